@@ -2,6 +2,7 @@
 """Throughput benchmark of the DD3D-DLA34 forward path (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last timed step's detections as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one forward pass of the hot path (uint8 image already resident in HBM -> final detections in HBM) over one
@@ -83,6 +84,9 @@ def parse_args():
                     help="a second issue geometry SLOTSxMICROBATCH timed in the same run and reported as config.alt_issue ('' skips it)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "r06_tower_hbm_bytes.json"),
                     help="PMC-derived HBM bytes per launch of the dominant kernel, keyed by kernel signature (see profiles/README.md)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the detections of the last timed step (the fields of the Instances a caller of "
+                         "the timed path receives) to DIR/<name>.npy: float fields as float32, integer fields as float64 (--gpus 1 only)")
     return ap.parse_args()
 
 
@@ -149,6 +153,7 @@ def main():
 
     rank, local, world = init_distributed()
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run"
+    assert not (args.dump_outputs and world > 1), "--dump-outputs covers the one-GPU run"
     assert torch.cuda.is_available(), "bench.py measures the HIP path; it needs an MI355X"
     dev = torch.device("cuda", local)
 
@@ -208,7 +213,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        runner.step()
+        last = runner.step()
     flush()
     torch.cuda.synchronize()
     barrier()
@@ -216,6 +221,8 @@ def main():
     elapsed_local = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed_local)
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:  # (before the repeated blocks and the other legs overwrite the detection buffers)
+        dump_outputs(args.dump_outputs, model, plan, last, request_inputs, B)
     # N > 1: every rank's own clock over the timed block and the device it ran on -- lets a reader of the line confirm that RCCL saw N
     # DISTINCT GPUs and that no rank idled (value itself uses the max over ranks, as the contract says)
     per_rank = None
@@ -458,6 +465,33 @@ def verify_work(runner, plan, B, microbatch=1):
         raise RuntimeError("bench: a synthetic image produced no detections: decode / NMS were not exercised")
     return {"slot_positions_checked": checked, "detections_per_image": [ref[k][0] for k in sorted(ref)], "distinct_images_per_slot": len(ref),
             "identical_across_slots": True}
+
+
+def dump_outputs(out_dir, model, plan, last, request_inputs, B):
+    """The detections of the last timed step -- request position j of the slot `last` (PipelinedForward.step's return), or the one plan of
+    `--pipeline 0` -- collected as a caller of the runner receives them (model.collect -> Instances) and written as DIR/<field>.npy,
+    concatenated over the step's B images (`detections_per_image` splits them).  The inputs are the seeded synthetic requests, so two
+    builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    if last is not None:
+        p, j = last.plan, last.fill - 1
+    else:
+        p, j = plan, 0
+    inp = request_inputs[j]
+    sizes = [(int(x["image"].shape[-2]), int(x["image"].shape[-1])) for x in inp]
+    outs = [o["instances"] for o in model.collect(p, inp, sizes, first=j * B)]
+    fields = {
+        "pred_boxes": lambda r: r.pred_boxes.tensor, "scores": lambda r: r.scores, "scores_3d": lambda r: r.scores_3d,
+        "pred_classes": lambda r: r.pred_classes, "locations": lambda r: r.locations, "fpn_levels": lambda r: r.fpn_levels,
+        "boxes3d_quat": lambda r: r.pred_boxes3d.quat, "boxes3d_proj_ctr": lambda r: r.pred_boxes3d.proj_ctr,
+        "boxes3d_depth": lambda r: r.pred_boxes3d.depth, "boxes3d_size": lambda r: r.pred_boxes3d.size,
+        "boxes3d_tvec": lambda r: r.pred_boxes3d.tvec, "boxes3d_corners": lambda r: r.pred_boxes3d.corners,
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, get in fields.items():
+        t = torch.cat([get(r).detach().cpu() for r in outs])
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy().astype(np.float32 if t.is_floating_point() else np.float64))
+    np.save(os.path.join(out_dir, "detections_per_image.npy"), np.array([len(r) for r in outs], dtype=np.float64))
 
 
 def _headroom(plans):

@@ -105,13 +105,16 @@ def test_bench_multi_gpu_command_line(hiplib, pipeline):
     assert d["work_verified"]["identical_across_slots"] and d["work_verified"]["detections_per_image"] == [100] * (1 if pipeline == "0" else 4)
 
 
-def test_bench_single_gpu_line_carries_parity_and_baselines(hiplib):
+def test_bench_single_gpu_line_carries_parity_and_baselines(hiplib, tmp_path):
     """The driver's N = 1 command (fewer CPU forwards): the ONE JSON line must carry the metric, the roofline object, the CPU baseline,
-    the parity object (the metric's second half: 3D-box L1 vs the oracle, bars met) and the read-back of the timed work."""
+    the parity object (the metric's second half: 3D-box L1 vs the oracle, bars met) and the read-back of the timed work.  With
+    --dump-outputs it also writes the detections of the last timed step as .npy files."""
     import json
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "outputs"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-forwards", "2", "--repeat-blocks", "1",
-           "--e2e-requests", "24"]
+           "--e2e-requests", "24", "--dump-outputs", str(dump)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd="/tmp")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -127,6 +130,14 @@ def test_bench_single_gpu_line_carries_parity_and_baselines(hiplib):
     assert pr["corners_l1_rel"] <= 1e-3 and pr["box3d_l1_tvec_size_rel"] <= 1e-3 and pr["box2d_rel_max"] <= 1e-3
     assert pr["int_mismatches"] == pr["rank_swaps"] or pr["on_cut_flips"] > 0  # same detections at the same ranks, up to score ties / cuts
     assert d["work_verified"]["slot_positions_checked"] == 20 and d["work_verified"]["distinct_images_per_slot"] == 4
+    # the last of the 20 timed steps is request position 19 % 4 of its slot: its detections, as a caller receives them
+    out = {f.name[:-4]: np.load(f) for f in dump.glob("*.npy")}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    n = d["work_verified"]["detections_per_image"][19 % 4]
+    assert out["detections_per_image"].tolist() == [n]
+    assert out["pred_boxes"].shape == (n, 4) and out["scores"].shape == out["scores_3d"].shape == out["pred_classes"].shape == (n,)
+    assert out["boxes3d_tvec"].shape == out["boxes3d_size"].shape == (n, 3) and out["boxes3d_corners"].shape == (n, 8, 3)
+    assert n > 0 and all(np.isfinite(a).all() for a in out.values())
     assert d["config"]["f16x2_range"]["overflow_headroom_x"] > 4
     assert d["config"]["bs1_images_per_s"] > 0 and "DLA34" in d["config"]["workload"]
     # the end-to-end leg (distinct host images through submit() / result(): core.py:65 ... :153-164) and the second issue geometry
