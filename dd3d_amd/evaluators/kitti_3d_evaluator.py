@@ -1,8 +1,10 @@
 """Result side of tridet/evaluators/kitti_3d_evaluator.py: `convert_3d_box_to_kitti` (:205-264) and `KITTI3DEvaluator.reset /
-process / prepare_kitti3d_submission` (:55-148, :197-202) with the same names, arguments and outputs, the box conversion running
-batched on the GPU (dd3d_amd.evaluators.formatting).  The AP engine (`evaluate`, `KITTIEvaluationEngine` :150-195, :267-1080) is
-host-side numba code outside the hot path; its overlap kernels are dd3d_amd.evaluators.rotate_iou.
+process / evaluate / prepare_kitti3d_submission` (:55-202) with the same names, arguments and outputs, the box conversion running
+batched on the GPU (dd3d_amd.evaluators.formatting) and the AP engine (`KITTIEvaluationEngine` :267-1099) on HIP kernels
+(dd3d_amd.evaluators.kitti_ap).
 """
+import itertools
+import json
 import os
 from collections import OrderedDict
 
@@ -11,6 +13,10 @@ import pandas as pd
 import torch
 
 from dd3d_amd.evaluators.formatting import format_boxes3d, kitti_tuple, xyxy_to_xywh
+from dd3d_amd.evaluators.kitti_ap import KITTIEvaluationEngine
+
+BBOX3D_PREDICTION_FILE = "bbox3d_predictions.json"
+KITTI_SUBMISSION_DIR = "kitti_3d_submission"
 
 
 def convert_3d_box_to_kitti(box):
@@ -35,15 +41,18 @@ def _xyxy_of(anno):
 
 class KITTI3DEvaluator:
     """`dataset_dicts` / `class_names` replace the detectron2 DatasetCatalog / MetadataCatalog lookups of the reference ctor
-    (:43-49); when detectron2 is installed and they are omitted the catalogs are used as in the reference."""
+    (:43-49); when detectron2 is installed and they are omitted the catalogs are used as in the reference.  `id_to_name` replaces
+    the catalog's `contiguous_id_to_name`; by default it is dict(enumerate(class_names)), which is what the KITTI dataset registers
+    (kitti_3d/build.py:309)."""
     def __init__(self, dataset_name=None, iou_thresholds=None, only_prepare_submission=False, output_dir=None, distributed=False, *,
-                 dataset_dicts=None, class_names=None):
+                 dataset_dicts=None, class_names=None, id_to_name=None):
         if dataset_dicts is None or class_names is None:
             from detectron2.data.catalog import DatasetCatalog, MetadataCatalog  # noqa: deliberate hard dependency of this branch
             dataset_dicts = DatasetCatalog.get(dataset_name) if dataset_dicts is None else dataset_dicts
             class_names = MetadataCatalog.get(dataset_name).thing_classes if class_names is None else class_names
         self._dataset_dicts = {d["file_name"]: d for d in dataset_dicts}
         self._class_names = list(class_names)
+        self._id_to_name = dict(enumerate(self._class_names)) if id_to_name is None else dict(id_to_name)
         self._iou_thresholds = iou_thresholds
         self._only_prepare_submission = only_prepare_submission
         self._output_dir = output_dir
@@ -103,9 +112,42 @@ class KITTI3DEvaluator:
             row += n_gt
 
     def evaluate(self):
-        raise NotImplementedError(
-            "the KITTI AP engine (kitti_3d_evaluator.py:150-195, :267-1080) is host code outside the hot path; feed "
-            "_predictions_kitti_format / _groundtruth_kitti_format to it, with dd3d_amd.evaluators.rotate_iou as its overlap kernels")
+        """kitti_3d_evaluator.py:150-195: OrderedDict kitti_box3d_r40/{class}_{Easy|Moderate|Hard}_{iou} then kitti_bev_r40/..., in
+        percent.  With distributed=True in a torch.distributed group of more than one process the three lists are gathered to rank 0
+        and every other rank returns None.  The predictions are written to `output_dir`/bbox3d_predictions.json; with output_dir=None
+        that file is not written (the reference needs a directory there).  only_prepare_submission writes the KITTI submission
+        files under `output_dir`/kitti_3d_submission and returns {}.  The AP engine runs on the GPU (KITTIEvaluationEngine)."""
+        if not self._only_prepare_submission and self._iou_thresholds is None:
+            raise ValueError("KITTI3DEvaluator.evaluate needs iou_thresholds: the reference passes EVALUATORS.KITTI3D.IOU_THRESHOLDS "
+                             "([0.5, 0.7] in configs/evaluators/kitti_3d.yaml)")
+        if self._only_prepare_submission and self._output_dir is None:
+            raise ValueError("KITTI3DEvaluator: only_prepare_submission writes the submission under output_dir, which is None")
+        predictions_as_json = self._predictions_as_json
+        predictions_kitti_format = self._predictions_kitti_format
+        groundtruth_kitti_format = self._groundtruth_kitti_format
+        import torch.distributed as dist
+        if self._distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            gathered = []
+            for part in (predictions_as_json, predictions_kitti_format, groundtruth_kitti_format):
+                dst = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+                dist.gather_object(part, dst, dst=0)
+                gathered.append(list(itertools.chain(*dst)) if dst is not None else None)
+            if dist.get_rank() != 0:
+                return None
+            predictions_as_json, predictions_kitti_format, groundtruth_kitti_format = gathered
+        if self._output_dir is not None:
+            os.makedirs(self._output_dir, exist_ok=True)
+            with open(os.path.join(self._output_dir, BBOX3D_PREDICTION_FILE), "w") as f:
+                json.dump(predictions_as_json, f, indent=4)
+        if self._only_prepare_submission:
+            self.prepare_kitti3d_submission(predictions_kitti_format, submission_dir=os.path.join(self._output_dir, KITTI_SUBMISSION_DIR))
+            return {}
+        assert len(predictions_kitti_format) == len(groundtruth_kitti_format)
+        formatted_predictions = [KITTIEvaluationEngine._format(idx, x, True) for idx, x in enumerate(predictions_kitti_format)]
+        formatted_groundtruth = [KITTIEvaluationEngine._format(idx, x, False) for idx, x in enumerate(groundtruth_kitti_format)]
+        engine = KITTIEvaluationEngine(id_to_name=self._id_to_name)
+        results = engine.evaluate(formatted_groundtruth, formatted_predictions, overlap_thresholds=self._iou_thresholds)
+        return OrderedDict({k: 100. * v for k, v in results.items()})
 
     @staticmethod
     def prepare_kitti3d_submission(predictions_kitti_format, submission_dir):

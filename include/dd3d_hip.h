@@ -540,6 +540,51 @@ int dd3d_image_box_overlap(const float* boxes, const float* qboxes, float* out, 
  * ------------------------------------------------------------------------------------------------ */
 int dd3d_format_boxes3d(const float* box3d, const float* quat_global, const float* speed, double* out, int32_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * KITTI 3D / BEV AP statistics (tridet/evaluators/kitti_3d_evaluator.py, KITTIEvaluationEngine.eval_metric :413-513).  The two
+ * greedy matchings of the reference's numba CPU code, over every (image, class x difficulty, overlap threshold[, score threshold])
+ * in one launch each:
+ *   dd3d_kitti_tp_scores  compute_threshold_jit :749-810 (pass 1): tp_score [n_cd][n_o][n_gt] float64 = the score of the detection
+ *                         a GT is matched to as a true positive, -inf for every other GT (ignored, unmatched, matched to an
+ *                         ignored detection).  The host collects the finite ones per (cd, o) for get_thresholds :813-847.
+ *   dd3d_kitti_pr_counts  compute_statistics_jit :910-1038 with compute_fp=True (pass 2), once per score threshold:
+ *                         tp_fp_fn [n_cd][n_o][t_max][3] int64 = (tp, fp, fn) summed over the images for thresh[cd][o][t],
+ *                         t < n_thresh[cd][o]; entries t >= n_thresh are 0.  The entry point zeroes the buffer on `stream`
+ *                         (hipMemsetAsync) before the launch.
+ * Inputs, all device memory except min_overlap:
+ *   ov          float32 overlap blocks, as dd3d_rotate_iou_eval / dd3d_d3_box_overlap leave them: image i's block is
+ *               [n_dt_i][n_gt_i] row-major at element ov_off[i] (detection rows, GT columns); n_ov = elements of `ov`
+ *   dt_begin / gt_begin  [n_img + 1] prefix offsets of each image's detections / GT in the per-box arrays
+ *   dt_score    [n_dt] float64 (compared in float64 throughout)
+ *   ign_dt / ign_gt  [n_cd][n_dt] / [n_cd][n_gt] int8 codes of clean_kitti_data :653-746 (-1 other class, 0 valid, 1 ignored)
+ *   min_overlap [n_o] float64, HOST memory, each >= -FLT_MAX; overlaps are compared against it in float64
+ *   max_dt / max_gt  upper bounds of the per-image counts (n_dt_i <= max_dt, n_gt_i <= max_gt)
+ * Caps: max_dt <= DD3D_KITTI_MAX_DT_PER_IMAGE, max_gt <= DD3D_KITTI_MAX_GT_PER_IMAGE, n_o <= DD3D_KITTI_MAX_OVERLAPS,
+ * t_max <= DD3D_KITTI_MAX_THRESHOLDS, n_cd * n_o <= 65535; larger inputs are rejected.  An image whose offsets break the declared
+ * bounds is skipped by the kernels (its outputs are left as they were) rather than read out of range.  Work with no image, no
+ * class x difficulty or no overlap threshold (or t_max = 0) returns 0 with nothing enqueued.  Results are deterministic: the
+ * counts are integers.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_KITTI_MAX_DT_PER_IMAGE 8192
+#define DD3D_KITTI_MAX_GT_PER_IMAGE 1024
+#define DD3D_KITTI_MAX_OVERLAPS 8
+#define DD3D_KITTI_MAX_THRESHOLDS 256
+typedef struct dd3d_kitti_match_args {  /* host memory */
+  const float* ov;
+  const int64_t* ov_off;
+  const int32_t* dt_begin;
+  const int32_t* gt_begin;
+  const double* dt_score;
+  const int8_t* ign_dt;
+  const int8_t* ign_gt;
+  const double* min_overlap;
+  int64_t n_ov;
+  int32_t n_img, n_dt, n_gt, n_cd, n_o, max_dt, max_gt;
+} dd3d_kitti_match_args;
+int dd3d_kitti_tp_scores(const dd3d_kitti_match_args* args, double* tp_score, void* stream);
+int dd3d_kitti_pr_counts(const dd3d_kitti_match_args* args, const double* thresh, const int32_t* n_thresh, int32_t t_max, int64_t* tp_fp_fn,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

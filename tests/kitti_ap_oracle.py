@@ -1,0 +1,170 @@
+"""Plain-Python statement of the KITTI AP statistics of tridet/evaluators/kitti_3d_evaluator.py, written loop for loop from the
+reference's numba code so that the HIP engine (dd3d_amd/evaluators/kitti_ap.py, dd3d_amd/csrc/kitti_ap.hip) has a CPU checker:
+
+    clean_kitti_data        :635-746   ignore codes per (class, difficulty)
+    tp_scores               :749-810   compute_threshold_jit (pass 1)
+    pr_counts               :910-1038  compute_statistics_jit with compute_fp=True (pass 2), tp / fp / fn only
+    get_thresholds          :813-847
+    eval_metric_counts      :440-513   eval_metric on given per-image overlaps: TP scores, thresholds, counts, recall, precision
+    results                 :342-414   r40 AP and the result keys of KITTIEvaluationEngine.evaluate
+
+Only the counts are restated: the yaw / similarity / match-degree / confidence / scale columns of `pr` never reach the result.
+The score cut of :947-950 is written `not (score >= thresh)`, which equals `score < thresh` for every number and drops a NaN
+score (the reference's fastmath build leaves that case undefined).
+"""
+from collections import OrderedDict
+
+import numpy as np
+
+LEVELS = {"max_occlusion": (0, 1, 2), "max_truncation": (0.15, 0.3, 0.5), "min_height": (40, 25, 25)}
+NO_DETECTION = float(np.finfo(np.float32).min)  # :771, :955
+
+
+def clean_kitti_data(gt_anno, dt_anno, current_class, difficulty, id_to_name, params=LEVELS):
+    """-> (num_valid_gt, ignored_gt, ignored_dt, dontcare boxes) of one image."""
+    cls = id_to_name[current_class].lower()
+    ignored_gt, ignored_dt, dontcare = [], [], []
+    num_valid = 0
+    for i in range(len(gt_anno["name"])):
+        box = gt_anno["bbox"][i]
+        name = gt_anno["name"][i].lower()
+        height = box[3] - box[1]
+        if name == cls:
+            kind = 1
+        elif (cls == "pedestrian" and name == "person_sitting") or (cls == "car" and name == "van"):
+            kind = 0  # a neighbouring class: neither rewarded nor penalised
+        else:
+            kind = -1
+        too_hard = (gt_anno["occluded"][i] > params["max_occlusion"][difficulty] or gt_anno["truncated"][i] > params["max_truncation"][difficulty]
+                    or height <= params["min_height"][difficulty])
+        if kind == 1 and not too_hard:
+            ignored_gt.append(0)
+            num_valid += 1
+        elif kind == 0 or (too_hard and kind == 1):
+            ignored_gt.append(1)
+        else:
+            ignored_gt.append(-1)
+        if name == "dontcare":
+            dontcare.append(box)
+    for i in range(len(dt_anno["name"])):
+        height = abs(dt_anno["bbox"][i, 3] - dt_anno["bbox"][i, 1])
+        if height < params["min_height"][difficulty]:
+            ignored_dt.append(1)
+        elif dt_anno["name"][i].lower() == cls:
+            ignored_dt.append(0)
+        else:
+            ignored_dt.append(-1)
+    return num_valid, ignored_gt, ignored_dt, dontcare
+
+
+def tp_scores(overlaps, scores, ignored_gt, ignored_dt, min_overlap):
+    """Pass 1 of one image: the scores of the detections matched to valid GT, GT order.  overlaps[det][gt] (float64)."""
+    assigned = [False] * len(scores)
+    out = []
+    for g in range(len(ignored_gt)):
+        if ignored_gt[g] == -1:
+            continue
+        pick, best = -1, NO_DETECTION
+        for d in range(len(scores)):
+            if ignored_dt[d] == -1 or assigned[d]:
+                continue
+            if overlaps[d][g] > min_overlap and scores[d] > best:
+                pick, best = d, scores[d]
+        if best == NO_DETECTION:
+            continue  # (a miss; pass 1 does not count it)
+        assigned[pick] = True
+        if not (ignored_gt[g] == 1 or ignored_dt[pick] == 1):
+            out.append(scores[pick])
+    return out
+
+
+def pr_counts(overlaps, scores, ignored_gt, ignored_dt, min_overlap, thresh):
+    """Pass 2 of one image at one score threshold -> (tp, fp, fn), through the reference's selection state machine (:955-991)."""
+    n = len(scores)
+    assigned = [False] * n
+    below = [not (scores[d] >= thresh) for d in range(n)]
+    tp = fn = 0
+    for g in range(len(ignored_gt)):
+        if ignored_gt[g] == -1:
+            continue
+        pick, found = -1, NO_DETECTION
+        max_overlap = NO_DETECTION
+        picked_ignored = False
+        for d in range(n):
+            if ignored_dt[d] == -1 or assigned[d] or below[d]:
+                continue
+            ov = overlaps[d][g]
+            if ov > min_overlap and (ov > max_overlap or picked_ignored) and ignored_dt[d] == 0:
+                max_overlap, pick, found, picked_ignored = ov, d, 1, False
+            elif ov > min_overlap and found == NO_DETECTION and ignored_dt[d] == 1:
+                pick, found, picked_ignored = d, 1, True
+        if found == NO_DETECTION and ignored_gt[g] == 0:
+            fn += 1
+        elif found != NO_DETECTION and (ignored_gt[g] == 1 or ignored_dt[pick] == 1):
+            assigned[pick] = True
+        elif found != NO_DETECTION:
+            tp += 1
+            assigned[pick] = True
+    fp = sum(1 for d in range(n) if not (assigned[d] or ignored_dt[d] == -1 or ignored_dt[d] == 1 or below[d]))
+    return tp, fp, fn
+
+
+def get_thresholds(scores, num_gt, num_sample_pts=41):
+    scores = sorted(scores, reverse=True)
+    current_recall = 0
+    out = []
+    for i, score in enumerate(scores):
+        l_recall = (i + 1) / num_gt
+        r_recall = (i + 2) / num_gt if i < len(scores) - 1 else l_recall
+        if (r_recall - current_recall) < (current_recall - l_recall) and i < len(scores) - 1:
+            continue
+        out.append(score)
+        current_recall += 1 / (num_sample_pts - 1.0)
+    return out
+
+
+def eval_metric_counts(overlaps, gt_annos, dt_annos, id_to_name, overlap_thresholds, sample_points=41):
+    """overlaps[i] = image i's [det][gt] block.  -> dict of per-(class, difficulty, overlap) lists and the curves."""
+    n_cls, n_o = len(id_to_name), len(overlap_thresholds)
+    recall = np.zeros([n_cls, 3, n_o, sample_points])
+    precision = np.zeros([n_cls, 3, n_o, sample_points])
+    out = {"tp_scores": {}, "thresholds": {}, "counts": {}, "ign_gt": {}, "ign_dt": {}}
+    for c in range(n_cls):
+        for diff in range(3):
+            cleaned = [clean_kitti_data(g, d, c, diff, id_to_name) for g, d in zip(gt_annos, dt_annos)]
+            num_valid = sum(x[0] for x in cleaned)
+            out["ign_gt"][c, diff] = [x[1] for x in cleaned]
+            out["ign_dt"][c, diff] = [x[2] for x in cleaned]
+            for o, mo in enumerate(overlap_thresholds):
+                per_image = [tp_scores(overlaps[i], dt_annos[i]["score"], x[1], x[2], mo) for i, x in enumerate(cleaned)]
+                scores = [s for p in per_image for s in p]
+                th = get_thresholds(scores, num_valid, sample_points)
+                counts = np.zeros((len(th), 3), dtype=np.int64)
+                for t, thr in enumerate(th):
+                    for i, x in enumerate(cleaned):
+                        counts[t] += pr_counts(overlaps[i], dt_annos[i]["score"], x[1], x[2], mo, thr)
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    pr = counts.astype(np.float64)
+                    recall[c, diff, o, :len(th)] = pr[:, 0] / (pr[:, 0] + pr[:, 2])
+                    precision[c, diff, o, :len(th)] = pr[:, 0] / (pr[:, 0] + pr[:, 1])
+                out["tp_scores"][c, diff, o] = per_image
+                out["thresholds"][c, diff, o] = th
+                out["counts"][c, diff, o] = counts
+    out["recall"], out["precision"] = recall, precision
+    return out
+
+
+def mean_ap(precision, recall, sample_points=41):
+    """get_mAP / get_sampled_precision_recall (:362-414)."""
+    spacing = [r for r in (1. / (sample_points - 1) * i for i in range(1, sample_points)) if 0.0 <= r <= 1.0]
+    return sum(((recall >= r) * precision).max(axis=3) for r in spacing) / len(spacing)
+
+
+def results(ap_3d, ap_bev, id_to_name, overlap_thresholds):
+    out = OrderedDict()
+    for prefix, ap in (("kitti_box3d_r40", ap_3d), ("kitti_bev_r40", ap_bev)):
+        for c, name in id_to_name.items():
+            for diff, dname in enumerate(["Easy", "Moderate", "Hard"]):
+                for o, thr in enumerate(overlap_thresholds):
+                    out[f"{prefix}/{name}_{dname}_{thr}"] = ap[c, diff, o]
+    return out
