@@ -318,7 +318,7 @@ def allocentric_to_egocentric(quat, proj_ctr, inv_K):
     R_obj_to_global = torch.bmm(R_local_to_global, R_obj_to_local)
     ego = matrix_to_quaternion(R_obj_to_global)
     qn = ego.norm(dim=1, keepdim=True)
-    renorm = not torch.allclose(qn, torch.as_tensor(1.), atol=1e-3)  # batch-global trigger, geometry.py:48-53
+    renorm = not torch.allclose(qn, torch.as_tensor(1., dtype=qn.dtype), atol=1e-3)  # batch-global trigger, geometry.py:48-53
     if renorm:
         ego = ego / qn.clamp(min=EPS)
     return ego, renorm

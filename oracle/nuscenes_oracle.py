@@ -172,8 +172,8 @@ def boxes_to_global(vec, pose_q, pose_t):
     matrix_to_quaternion ([ext] pytorch3d Transform3d row-vector algebra folded)."""
     quat, tvec, wlh = vec[:, :4], vec[:, 4:7], vec[:, 7:10]
     R_SO = O.quaternion_to_matrix(quat)
-    R_WS = O.quaternion_to_matrix(torch.as_tensor(pose_q, dtype=torch.float32))
-    t_WS = torch.as_tensor(pose_t, dtype=torch.float32)
+    R_WS = O.quaternion_to_matrix(torch.as_tensor(pose_q, dtype=vec.dtype))  # float32 in the forward; float64 in for a float64 reference
+    t_WS = torch.as_tensor(pose_t, dtype=vec.dtype)
     R_WO = torch.matmul(R_WS.unsqueeze(0), R_SO)
     t_WO = torch.matmul(tvec, R_WS.T) + t_WS
     return torch.cat([O.matrix_to_quaternion(R_WO), t_WO, wlh], dim=1)

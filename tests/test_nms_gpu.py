@@ -17,9 +17,10 @@ pytestmark = pytest.mark.gpu
 IDX_FIELD = 8  # a candidate field dd3d_nms_finalize copies verbatim into the detection row: carries the candidate's index here
 
 
-def _run(levels, thr, post_topk, use_score3d=1, slots=None):
+def _run(levels, thr, post_topk, use_score3d=1, slots=None, record=None, out_size=None, do_postprocess=0):
     """levels: per image, a list (one entry per level) of dicts boxes [m,4], score, score3d, cls.  Returns per image the candidate
-    indices (position in the level-major concatenation) of the detections, in output order."""
+    indices (position in the level-major concatenation) of the detections, in output order.  record = (img_first, img_per_rec,
+    pad_words): cand / counts / out_size are read from padded records (ABI 3) instead of dense arrays."""
     from dd3d_amd import hip
     lib = hip.lib()
     dev = torch.device("cuda")
@@ -47,20 +48,37 @@ def _run(levels, thr, post_topk, use_score3d=1, slots=None):
             cand[g, 6, sl] = lv["cls"].to(torch.int32).view(torch.float32)
             cand[g, IDX_FIELD, sl] = torch.arange(run, run + m, dtype=torch.float32)
             run += m
-    cand, counts = cand.to(dev), counts.to(dev)
+    osz = torch.ones((G, 4), dtype=torch.float32) if out_size is None else torch.as_tensor(out_size, dtype=torch.float32)
+    if record is not None:  # record r = [P images' cand | P images' counts | P images' out_size | pad], image g at img_first + g
+        first, P, pad = record
+        FN = hip.CAND_FIELDS * NS
+        stride = P * (FN + L + 4) + pad
+        nrec = (first + G + P - 1) // P
+        buf = torch.full((nrec, stride), float("nan"), dtype=torch.float32)
+        for g in range(G):
+            r, j = divmod(first + g, P)
+            buf[r, j * FN:(j + 1) * FN] = cand[g].reshape(-1)
+            buf[r, P * FN + j * L:P * FN + (j + 1) * L] = counts[g].view(torch.float32)
+            buf[r, P * (FN + L) + j * 4:P * (FN + L) + j * 4 + 4] = osz[g]
+        buf = buf.to(dev)
+    cand, counts, osz = cand.to(dev), counts.to(dev), osz.to(dev)
     ncap = (NS + 63) // 64 * 64
     det_cap = max(1, NS)
     w = dict(sort_idx=torch.zeros((G, ncap), dtype=torch.int32, device=dev), sbox=torch.zeros((G, ncap, 4), dtype=torch.float32, device=dev),
              scls=torch.zeros((G, ncap), dtype=torch.int32, device=dev), mask=torch.full((G, ncap, ncap // 64), -1, dtype=torch.int64, device=dev),
              nvalid=torch.zeros((G, 2), dtype=torch.int32, device=dev), det=torch.zeros((G, det_cap, hip.DET_FIELDS), dtype=torch.float32, device=dev),
-             det_count=torch.zeros((G, ), dtype=torch.int32, device=dev), out_size=torch.ones((G, 4), dtype=torch.float32, device=dev))
+             det_count=torch.zeros((G, ), dtype=torch.int32, device=dev), out_size=osz)
     a = hip.NmsArgs()
     a.cand, a.counts, a.G, a.num_levels, a.topk = cand.data_ptr(), counts.data_ptr(), G, L, topk
-    a.do_nms, a.use_score3d, a.nms_thresh, a.post_topk, a.do_postprocess = 1, use_score3d, float(thr), post_topk, 0
+    a.do_nms, a.use_score3d, a.nms_thresh, a.post_topk, a.do_postprocess = 1, use_score3d, float(thr), post_topk, do_postprocess
     a.out_size, a.sort_idx, a.sbox, a.scls = w["out_size"].data_ptr(), w["sort_idx"].data_ptr(), w["sbox"].data_ptr(), w["scls"].data_ptr()
     a.mask, a.nvalid, a.det, a.det_count, a.det_cap = w["mask"].data_ptr(), w["nvalid"].data_ptr(), w["det"].data_ptr(), w["det_count"].data_ptr(), det_cap
     for i, v in enumerate(slot_off):
         a.slot_off[i] = v
+    if record is not None:
+        base = buf.data_ptr()
+        a.cand, a.counts, a.out_size = base, base + 4 * P * FN, base + 4 * P * (FN + L)
+        a.img_first, a.img_per_rec, a.rec_stride = first, P, stride
     hip.check(lib.dd3d_nms_finalize(C.byref(a), hip.current_stream()), "nms")
     torch.cuda.synchronize()
     cnt = w["det_count"].cpu().tolist()
@@ -162,3 +180,16 @@ def test_nms_disabled_and_threshold_zero_pass_everything_in_input_order(hiplib):
     assert got[0] == list(range(400))
     got, _, _ = _run([img], 0.0, 100)
     assert got[0] == _expect(img, 0.0, 100)
+
+
+def test_record_addressing_is_bit_identical_to_dense(hiplib):
+    """img_per_rec > 0 (ABI 3): cand, counts and out_size read from padded records, starting at img_first, must give the dense result."""
+    gen = torch.Generator().manual_seed(19)
+    slots = [300, 120, 40]
+    imgs = [[_level(gen, m, "clusters") for m in fill] for fill in ([300, 100, 7], [0, 0, 0], [120, 120, 40], [5, 0, 33], [250, 60, 1])]
+    osz = [[375.0 + 10 * g, 1242.0 - g, 900.0, 1600.0 + g] for g in range(len(imgs))]
+    got, det, cnt = _run(imgs, 0.75, 100, slots=slots, out_size=osz, do_postprocess=1)
+    for record in ((0, 1, 3), (2, 3, 7), (5, 2, 1)):
+        got_r, det_r, cnt_r = _run(imgs, 0.75, 100, slots=slots, out_size=osz, do_postprocess=1, record=record)
+        assert cnt_r == cnt and got_r == got, record
+        assert torch.equal(det_r.view(torch.int32), det.view(torch.int32)), record
