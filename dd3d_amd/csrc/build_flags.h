@@ -81,49 +81,29 @@
 #else
 #define DD3D_BF_13 ""
 #endif
-#ifdef DD3D_CHAIN_A_AUX
-#define DD3D_BF_14 " DD3D_CHAIN_A_AUX=" DD3D_BF_STR(DD3D_CHAIN_A_AUX)
+#ifdef DD3D_ROW_STAMP
+#define DD3D_BF_14 " DD3D_ROW_STAMP=" DD3D_BF_STR(DD3D_ROW_STAMP)
 #else
 #define DD3D_BF_14 ""
 #endif
-#ifdef DD3D_CHAIN_ACQUIRE
-#define DD3D_BF_15 " DD3D_CHAIN_ACQUIRE=" DD3D_BF_STR(DD3D_CHAIN_ACQUIRE)
+#ifdef DD3D_ROW_B_WAVES
+#define DD3D_BF_15 " DD3D_ROW_B_WAVES=" DD3D_BF_STR(DD3D_ROW_B_WAVES)
 #else
 #define DD3D_BF_15 ""
 #endif
-#ifdef DD3D_CHAIN_RES_SC1
-#define DD3D_BF_16 " DD3D_CHAIN_RES_SC1=" DD3D_BF_STR(DD3D_CHAIN_RES_SC1)
+#ifdef DD3D_ROW_B_SADDR
+#define DD3D_BF_16 " DD3D_ROW_B_SADDR=" DD3D_BF_STR(DD3D_ROW_B_SADDR)
 #else
 #define DD3D_BF_16 ""
 #endif
-#ifdef DD3D_CHAIN_B_FIRST
-#define DD3D_BF_17 " DD3D_CHAIN_B_FIRST=" DD3D_BF_STR(DD3D_CHAIN_B_FIRST)
+#ifdef DD3D_ROW_B_WAVES_HI
+#define DD3D_BF_17 " DD3D_ROW_B_WAVES_HI=" DD3D_BF_STR(DD3D_ROW_B_WAVES_HI)
 #else
 #define DD3D_BF_17 ""
 #endif
-#ifdef DD3D_ROW_STAMP
-#define DD3D_BF_18 " DD3D_ROW_STAMP=" DD3D_BF_STR(DD3D_ROW_STAMP)
+#ifdef DD3D_ROW_PRIO_SLICE
+#define DD3D_BF_18 " DD3D_ROW_PRIO_SLICE=" DD3D_BF_STR(DD3D_ROW_PRIO_SLICE)
 #else
 #define DD3D_BF_18 ""
 #endif
-#ifdef DD3D_ROW_B_WAVES
-#define DD3D_BF_19 " DD3D_ROW_B_WAVES=" DD3D_BF_STR(DD3D_ROW_B_WAVES)
-#else
-#define DD3D_BF_19 ""
-#endif
-#ifdef DD3D_ROW_B_SADDR
-#define DD3D_BF_20 " DD3D_ROW_B_SADDR=" DD3D_BF_STR(DD3D_ROW_B_SADDR)
-#else
-#define DD3D_BF_20 ""
-#endif
-#ifdef DD3D_ROW_B_WAVES_HI
-#define DD3D_BF_21 " DD3D_ROW_B_WAVES_HI=" DD3D_BF_STR(DD3D_ROW_B_WAVES_HI)
-#else
-#define DD3D_BF_21 ""
-#endif
-#ifdef DD3D_ROW_PRIO_SLICE
-#define DD3D_BF_22 " DD3D_ROW_PRIO_SLICE=" DD3D_BF_STR(DD3D_ROW_PRIO_SLICE)
-#else
-#define DD3D_BF_22 ""
-#endif
-#define DD3D_BUILD_FLAGS DD3D_BF_0 DD3D_BF_1 DD3D_BF_2 DD3D_BF_3 DD3D_BF_4 DD3D_BF_5 DD3D_BF_6 DD3D_BF_7 DD3D_BF_8 DD3D_BF_9 DD3D_BF_10 DD3D_BF_11 DD3D_BF_12 DD3D_BF_13 DD3D_BF_14 DD3D_BF_15 DD3D_BF_16 DD3D_BF_17 DD3D_BF_18 DD3D_BF_19 DD3D_BF_20 DD3D_BF_21 DD3D_BF_22
+#define DD3D_BUILD_FLAGS DD3D_BF_0 DD3D_BF_1 DD3D_BF_2 DD3D_BF_3 DD3D_BF_4 DD3D_BF_5 DD3D_BF_6 DD3D_BF_7 DD3D_BF_8 DD3D_BF_9 DD3D_BF_10 DD3D_BF_11 DD3D_BF_12 DD3D_BF_13 DD3D_BF_14 DD3D_BF_15 DD3D_BF_16 DD3D_BF_17 DD3D_BF_18

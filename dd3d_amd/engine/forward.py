@@ -43,7 +43,6 @@ class ForwardPlan(PlanBase, BackboneLowering):
         self._trunk(model, B, Hp, Wp)
         # ---- heads + post-processing
         self._heads(model, self.features)
-        self.merge_chains()  # (before the ops are counted: dependent 3 x 3 convolutions of the trunk / the tower layers become chain launches)
         self._postprocess(model, world_size, rank)
 
     def _trunk(self, model, B, Hp, Wp):
@@ -482,8 +481,6 @@ class ForwardPlan(PlanBase, BackboneLowering):
         # (DenseDepthPlan shares this class without the post-processing half: no exchange, no gathered buffer)
         if not (getattr(self, "exchange", False) and self.math == hip.MATH_F16X2 and getattr(self, "gathered", None) is not None):
             return super().check_status(rb)
-        if (int(self.status.cpu()) if rb is None else rb.status) & hip.STATUS_CHAIN_TIMEOUT:
-            return super().check_status(rb)  # (raises: a rank-local launch fault, not a numeric verdict the ranks share)
         if rb is not None and rb.flags.shape[0] == self.world_size:
             fl = rb.flags
         else:
