@@ -1,11 +1,19 @@
-"""Result side of tridet/evaluators/nuscenes_evaluator.py: `NuscenesEvaluator.reset / process / build_nusc_detection` (:138-247)
-with the same names and outputs; attribute naming on the host, the global velocity of every detection of the call in one launch
-(dd3d_amd.evaluators.formatting).  `evaluate` (:249-330) drives the nuScenes devkit, which is outside the hot path.
+"""Result side of tridet/evaluators/nuscenes_evaluator.py: `NuscenesEvaluator.reset / process / build_nusc_detection / evaluate`
+(:138-312) with the same names and outputs; attribute naming on the host, the global velocity of every detection of the call in one
+launch (dd3d_amd.evaluators.formatting).  `evaluate` writes the reference's two files and computes the nuScenes detection metrics with
+the HIP engine of dd3d_amd.evaluators.nuscenes_eval in place of the devkit's `DetectionEval`.
 """
+import itertools
+import json
+import os
 from collections import OrderedDict, defaultdict
 
 from dd3d_amd.evaluators.formatting import format_boxes3d, xyxy_to_xywh
+from dd3d_amd.evaluators.nuscenes_eval import NuscenesDetectionEval, NuscenesGroundTruth
 from dd3d_amd.modeling.nuscenes_dd3d import get_group_idxs
+
+BBOX3D_PREDICTION_FILE = "bbox3d_predictions.json"
+NUSC_SUBMISSION_FILE = "nuscenes_submission.json"
 
 NUM_IMAGES_PER_SAMPLE = 6
 # tridet/data/datasets/nuscenes/build.py:50-61 (CATEGORY_IDS order)
@@ -23,6 +31,23 @@ CYC_ATTR_CLASSES = ("bicycle", "motorcycle")
 VEH_ATTR_ID_TO_NAME = {0: "vehicle.moving", 1: "vehicle.parked", 2: "vehicle.stopped"}
 PED_ATTR_ID_TO_NAME = {0: "pedestrian.moving", 1: "pedestrian.standing", 2: "pedestrian.sitting_lying_down"}
 CYC_ATTR_ID_TO_NAME = {0: "cycle.with_rider", 1: "cycle.without_rider"}
+# tridet/data/datasets/nuscenes/build.py:27-35
+DATASET_NAME_TO_VERSION = {
+    "nusc_train": "v1.0-trainval", "nusc_val": "v1.0-trainval", "nusc_val-subsample-8": "v1.0-trainval", "nusc_trainval": "v1.0-trainval",
+    "nusc_test": "v1.0-test", "nusc_mini_train": "v1.0-mini", "nusc_mini_val": "v1.0-mini"
+}
+# nuscenes_evaluator.py:45-55
+DATASET_NAME_TO_EVAL_SET = {
+    "nusc_train": "train", "nusc_val": "val", "nusc_val-subsample-8": "val", "nusc_test": "test", "nusc_mini_train": "mini_train",
+    "nusc_mini_val": "mini_val", "nusc_train_detect": "train_detect", "nusc_train_track": "train_track"
+}
+# nuscenes_evaluator.py:268-274
+EVAL_META = {"use_camera": True, "use_lidar": False, "use_radar": False, "use_map": False, "use_external": True}
+
+
+class NuscenesEvaluationUnavailable(NotImplementedError):
+    """evaluate() cannot produce what was asked: the test split without an output_dir, or another split with neither
+    `ground_truth=` nor the nuScenes devkit."""
 
 
 def attribute_name(class_name, attr):
@@ -33,12 +58,32 @@ def attribute_name(class_name, attr):
     return ""
 
 
+def _gather_dict(dikt):
+    """tridet/utils/comm.py:71-88 gather_dict: the dicts of every rank merged on rank 0 (keys disjoint across ranks), None elsewhere."""
+    import torch.distributed as dist
+    dst = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+    dist.gather_object(dikt, dst, dst=0)
+    if dst is None:
+        return None
+    gathered = {}
+    for d in dst:
+        for k in d.keys():
+            assert k not in gathered, f"Dictionary key overlaps: {k}"
+        gathered.update(d)
+    return gathered
+
+
 class NuscenesEvaluator:
-    def __init__(self, nusc_root=None, dataset_name=None, output_dir=None):
+    """`ground_truth` (a NuscenesGroundTruth or the path of its JSON) replaces the devkit's `load_gt` on the dataset; without it the
+    devkit is used when it is installed and `nusc_root` is set, as in the reference.  `distributed=True` gathers to rank 0, as the
+    reference does whenever it runs distributed."""
+    def __init__(self, nusc_root=None, dataset_name=None, output_dir=None, *, ground_truth=None, distributed=False):
         self._nusc_root = nusc_root
         self._dataset_name = dataset_name
         self._output_dir = output_dir
         self._only_make_submission_file = dataset_name == "nusc_test"
+        self._ground_truth = ground_truth
+        self._distributed = distributed
         self.reset()
 
     def reset(self):
@@ -83,5 +128,48 @@ class NuscenesEvaluator:
             "velocity": [0., .0] if velocity is None else velocity
         }
 
+    def _load_ground_truth(self):
+        gt = self._ground_truth
+        if isinstance(gt, NuscenesGroundTruth):
+            return gt
+        if gt is not None:
+            return NuscenesGroundTruth.from_json(os.fspath(gt))
+        if self._nusc_root is None:
+            return None
+        try:
+            from nuscenes import NuScenes
+        except ImportError:
+            return None
+        nusc = NuScenes(version=DATASET_NAME_TO_VERSION[self._dataset_name], dataroot=self._nusc_root, verbose=True)
+        return NuscenesGroundTruth.from_devkit(nusc, DATASET_NAME_TO_EVAL_SET[self._dataset_name])
+
     def evaluate(self):
-        raise NotImplementedError("nuscenes_evaluator.py:249-330 runs the nuScenes devkit on _nusc_sample_results; outside the hot path")
+        """nuscenes_evaluator.py:249-312.  Writes `output_dir`/bbox3d_predictions.json and nuscenes_submission.json (with the
+        reference's meta block) when output_dir is set; the test split then returns {}.  Otherwise returns what the devkit's
+        `DetectionMetrics.serialize()` returns minus cfg and eval_time: label_aps, mean_dist_aps, mean_ap, label_tp_errors, tp_errors,
+        tp_scores, nd_score.  With distributed=True in a group of more than one process, ranks other than 0 return None."""
+        predictions_as_json, nusc_sample_results = self._predictions_as_json, self._nusc_sample_results
+        import torch.distributed as dist
+        if self._distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dst = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+            dist.gather_object(predictions_as_json, dst, dst=0)
+            nusc_sample_results = _gather_dict(dict(nusc_sample_results))
+            if dist.get_rank() != 0:
+                return None
+            predictions_as_json = list(itertools.chain(*dst))
+        if self._output_dir is not None:
+            os.makedirs(self._output_dir, exist_ok=True)
+            with open(os.path.join(self._output_dir, BBOX3D_PREDICTION_FILE), "w") as f:
+                json.dump(predictions_as_json, f, indent=4)
+            with open(os.path.join(self._output_dir, NUSC_SUBMISSION_FILE), "w") as f:
+                json.dump({"meta": EVAL_META, "results": nusc_sample_results}, f, indent=4)
+        if self._only_make_submission_file:
+            if self._output_dir is None:
+                raise NuscenesEvaluationUnavailable(f"NuscenesEvaluator({self._dataset_name!r}): the test split only makes the submission "
+                                                    "file, and output_dir is None")
+            return {}
+        gt = self._load_ground_truth()
+        if gt is None:
+            raise NuscenesEvaluationUnavailable(f"NuscenesEvaluator({self._dataset_name!r}): no ground truth: pass ground_truth= (a "
+                                                "NuscenesGroundTruth or its JSON), or install the nuScenes devkit and set nusc_root")
+        return NuscenesDetectionEval(gt).evaluate(nusc_sample_results)

@@ -136,12 +136,23 @@ class KittiMatchArgs(C.Structure):
 
 KITTI_MAX_DT_PER_IMAGE, KITTI_MAX_GT_PER_IMAGE, KITTI_MAX_OVERLAPS, KITTI_MAX_THRESHOLDS = 8192, 1024, 8, 256
 
+NUSC_MAX_PRED_PER_SEGMENT, NUSC_MAX_GT_PER_SEGMENT, NUSC_MAX_THRESHOLDS = 500, 4096, 8
+
+
+class NuscMatchArgs(C.Structure):
+    """`dd3d_nusc_match_args`."""
+    _fields_ = [
+        ("pred_xy", C.c_void_p), ("gt_xy", C.c_void_p), ("pred_begin", C.c_void_p), ("gt_begin", C.c_void_p), ("pred_begin_host", C.c_void_p),
+        ("gt_begin_host", C.c_void_p), ("n_seg", C.c_int32), ("n_pred", C.c_int32), ("n_gt", C.c_int32), ("n_thr", C.c_int32),
+        ("thr", C.c_double * NUSC_MAX_THRESHOLDS)
+    ]
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
     "dd3d_invert_intrinsics", "dd3d_nms_finalize", "dd3d_bev_nms_aggregate", "dd3d_conv2d_smallc_supported", "dd3d_conv2d_smallc_bf16x3", "dd3d_rotate_iou_eval", "dd3d_d3_box_overlap", "dd3d_image_box_overlap", "dd3d_aligned_bilinear_scale", "dd3d_resize_bilinear_u8",
     "dd3d_format_boxes3d", "dd3d_math_planes", "dd3d_split_planes", "dd3d_maxpool2x2_planes", "dd3d_maxpool2x2_planes_in", "dd3d_upsample2x_add_planes", "dd3d_ese_fused", "dd3d_stem_fused_f16x2", "dd3d_fold_range_flags", "dd3d_pack_readback",
-    "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts"
+    "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match"
 ]
 
 
@@ -208,6 +219,7 @@ def lib():
     L.dd3d_split_planes.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_void_p, C.c_void_p]
     L.dd3d_kitti_tp_scores.argtypes = [C.POINTER(KittiMatchArgs), C.c_void_p, C.c_void_p]
     L.dd3d_kitti_pr_counts.argtypes = [C.POINTER(KittiMatchArgs), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dd3d_nusc_center_match.argtypes = [C.POINTER(NuscMatchArgs), C.c_void_p, C.c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

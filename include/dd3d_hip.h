@@ -568,6 +568,38 @@ int dd3d_kitti_tp_scores(const dd3d_kitti_match_args* args, double* tp_score, vo
 int dd3d_kitti_pr_counts(const dd3d_kitti_match_args* args, const double* thresh, const int32_t* n_thresh, int32_t t_max, int64_t* tp_fp_fn,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * nuScenes detection matching (the nuScenes devkit's `accumulate`, detection_cvpr_2019, driven by
+ * tridet/evaluators/nuscenes_evaluator.py:249-312).  The greedy centre-distance matching of every (sample, class) segment at every
+ * distance threshold, in one launch:
+ *   match [n_thr][n_pred] int32 = the GT row (index into gt_xy) that prediction row p is matched to at threshold t, or -1.
+ * Inputs (device memory unless marked HOST):
+ *   pred_xy     [n_pred][2] float64 prediction centres (x, y); each segment's rows are in matching order (the host sorts them)
+ *   gt_xy       [n_gt][2] float64 GT centres (x, y); each segment's rows are its sample's GT of the class, in the sample's order
+ *   pred_begin / gt_begin            [n_seg + 1] int32 offsets of each segment's rows (CSR)
+ *   pred_begin_host / gt_begin_host  HOST copies of the same offsets, validated before the launch
+ *   thr         n_thr distance thresholds, by value
+ * For each prediction in order, the untaken GT of its segment at the smallest distance sqrt(dx*dx + dy*dy) (float64, correctly
+ * rounded, lowest row on ties; NaN never matches) is matched iff that distance < thr[t], and is then taken.
+ * Caps: n_thr in [1, DD3D_NUSC_MAX_THRESHOLDS], at most DD3D_NUSC_MAX_PRED_PER_SEGMENT predictions and DD3D_NUSC_MAX_GT_PER_SEGMENT GT
+ * per segment, n_seg <= 262140, offsets monotone within [0, n_pred] / [0, n_gt]; anything else is rejected.  Rows outside every segment
+ * are not written.  No segment or no prediction returns 0 with nothing enqueued.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_NUSC_MAX_PRED_PER_SEGMENT 500
+#define DD3D_NUSC_MAX_GT_PER_SEGMENT 4096
+#define DD3D_NUSC_MAX_THRESHOLDS 8
+typedef struct dd3d_nusc_match_args {  /* host memory */
+  const double* pred_xy;
+  const double* gt_xy;
+  const int32_t* pred_begin;
+  const int32_t* gt_begin;
+  const int32_t* pred_begin_host;
+  const int32_t* gt_begin_host;
+  int32_t n_seg, n_pred, n_gt, n_thr;
+  double thr[DD3D_NUSC_MAX_THRESHOLDS];
+} dd3d_nusc_match_args;
+int dd3d_nusc_center_match(const dd3d_nusc_match_args* args, int32_t* match, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
