@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "box3d_decode.h"
 
 DD3D_NOTE_BUILD_FLAGS
 
@@ -314,73 +315,17 @@ __global__ __launch_bounds__(PT) void fcos_select_decode_kernel(const SelectK P)
       const int C3 = a.class_agnostic_3d ? 1 : C;
       const int c3 = a.class_agnostic_3d ? 0 : c;
       const float* p = b3d + (pix0 + loc) * a.b3d_pitch;  // channel = component * C3 + class  (fcos3d.py:335-339)
-      float qa = p[0 * C3 + c3], qb = p[1 * C3 + c3], qc = p[2 * C3 + c3], qd = p[3 * C3 + c3];
-      float cx = p[4 * C3 + c3], cy = p[5 * C3 + c3];
-      float depth = p[6 * C3 + c3];
-      const float s0 = p[7 * C3 + c3], s1 = p[8 * C3 + c3], s2 = p[9 * C3 + c3];
       const float conf = sigmoidf(p[10 * C3 + c3]);
       cand[5 * NS + tid] = score * conf;  // scores_3d, fcos3d.py:375-376
-      const float* K = a.inv_K + 9 * b;
-      // quat / max(|quat|, eps), then / |quat| again  (fcos3d.py:31-34)
-      float nrm = fmaxf(sqrtf(qa * qa + qb * qb + qc * qc + qd * qd), QEPS);
-      qa /= nrm, qb /= nrm, qc /= nrm, qd /= nrm;
-      nrm = sqrtf(qa * qa + qb * qb + qc * qc + qd * qd);
-      qa /= nrm, qb /= nrm, qc /= nrm, qd /= nrm;
-      if (a.scale_depth_by_focal) {  // fcos3d.py:36-38
-        const float pixel_size = sqrtf(K[0] * K[0] + K[4] * K[4]);
-        depth = depth / (pixel_size * a.focal_factor);
-      }
-      if (a.depth_is_distance) {  // fcos3d.py:40-41, ray through the *location*
-        const float rx = K[0] * lx + K[1] * ly + K[2], ry = K[3] * lx + K[4] * ly + K[5], rz = K[6] * lx + K[7] * ly + K[8];
-        depth = depth / fmaxf(sqrtf(rx * rx + ry * ry + rz * rz), QEPS);
-      }
-      depth = fminf(fmaxf(depth, a.min_depth), a.max_depth);
-      cx += lx, cy += ly;  // proj_ctr + locations
-      if (a.allocentric) {
-        // R_obj_to_local = M(q)  ([ext] pytorch3d quaternion_to_matrix)
-        const float two_s = 2.0f / (qa * qa + qb * qb + qc * qc + qd * qd);
-        const float o00 = 1 - two_s * (qc * qc + qd * qd), o01 = two_s * (qb * qc - qd * qa), o02 = two_s * (qb * qd + qc * qa);
-        const float o10 = two_s * (qb * qc + qd * qa), o11 = 1 - two_s * (qb * qb + qd * qd), o12 = two_s * (qc * qd - qb * qa);
-        const float o20 = two_s * (qb * qd - qc * qa), o21 = two_s * (qc * qd + qb * qa), o22 = 1 - two_s * (qb * qb + qc * qc);
-        // local frame from the viewing ray through proj_ctr  (geometry.py:30-41)
-        float zx = K[0] * cx + K[1] * cy + K[2], zy = K[3] * cx + K[4] * cy + K[5], zz = K[6] * cx + K[7] * cy + K[8];
-        const float zn = sqrtf(zx * zx + zy * zy + zz * zz);
-        zx /= zn, zy /= zn, zz /= zn;
-        float yx = 0.f - zy * zx, yy = 1.f - zy * zy, yz = 0.f - zy * zz;
-        const float yn = sqrtf(yx * yx + yy * yy + yz * yz);
-        yx /= yn, yy /= yn, yz /= yn;
-        const float xx = yy * zz - yz * zy, xy = yz * zx - yx * zz, xz = yx * zy - yy * zx;  // cross(y, z)
-        // R = [x y z] (columns) * R_obj
-        const float m00 = xx * o00 + yx * o10 + zx * o20, m01 = xx * o01 + yx * o11 + zx * o21, m02 = xx * o02 + yx * o12 + zx * o22;
-        const float m10 = xy * o00 + yy * o10 + zy * o20, m11 = xy * o01 + yy * o11 + zy * o21, m12 = xy * o02 + yy * o12 + zy * o22;
-        const float m20 = xz * o00 + yz * o10 + zz * o20, m21 = xz * o01 + yz * o11 + zz * o21, m22 = xz * o02 + yz * o12 + zz * o22;
-        // [ext] pytorch3d matrix_to_quaternion (0.5.x/0.6.x): candidate of the largest |component|, no sign canonicalisation
-        const float t0 = 1.f + m00 + m11 + m22, t1 = 1.f + m00 - m11 - m22, t2 = 1.f - m00 + m11 - m22, t3 = 1.f - m00 - m11 + m22;
-        const float a0 = t0 > 0.f ? sqrtf(t0) : 0.f, a1 = t1 > 0.f ? sqrtf(t1) : 0.f;
-        const float a2 = t2 > 0.f ? sqrtf(t2) : 0.f, a3 = t3 > 0.f ? sqrtf(t3) : 0.f;
-        int best = 0;
-        float am = a0;
-        if (a1 > am) best = 1, am = a1;
-        if (a2 > am) best = 2, am = a2;
-        if (a3 > am) best = 3, am = a3;
-        const float den = 2.0f * fmaxf(am, 0.1f);
-        if (best == 0) q0 = a0 * a0, q1 = m21 - m12, q2 = m02 - m20, q3 = m10 - m01;
-        else if (best == 1) q0 = m21 - m12, q1 = a1 * a1, q2 = m10 + m01, q3 = m02 + m20;
-        else if (best == 2) q0 = m02 - m20, q1 = m10 + m01, q2 = a2 * a2, q3 = m12 + m21;
-        else q0 = m10 - m01, q1 = m20 + m02, q2 = m21 + m12, q3 = a3 * a3;
-        q0 /= den, q1 /= den, q2 /= den, q3 /= den;
-        qn = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-        bad = !(fabsf(qn - 1.0f) <= 1e-3f + 1e-5f);  // torch.allclose(qn, 1, atol=1e-3) with the default rtol
-      } else {
-        q0 = qa, q1 = qb, q2 = qc, q3 = qd;
-      }
-      const float* cs = a.canon_sizes + 3 * c;
-      cand[14 * NS + tid] = cx;
-      cand[15 * NS + tid] = cy;
-      cand[16 * NS + tid] = depth;
-      cand[17 * NS + tid] = (tanhf(s0) + 1.0f) * cs[0];
-      cand[18 * NS + tid] = (tanhf(s1) + 1.0f) * cs[1];
-      cand[19 * NS + tid] = (tanhf(s2) + 1.0f) * cs[2];
+      const Box3dDecodeParams dp{a.scale_depth_by_focal, a.depth_is_distance, a.allocentric, a.focal_factor, a.min_depth, a.max_depth};
+      const Box3dDecoded d = decode_box3d(p, C3, c3, lx, ly, a.inv_K + 9 * b, a.canon_sizes + 3 * c, dp);  // box3d_decode.h
+      q0 = d.q0, q1 = d.q1, q2 = d.q2, q3 = d.q3, qn = d.qn, bad = d.bad;
+      cand[14 * NS + tid] = d.cx;
+      cand[15 * NS + tid] = d.cy;
+      cand[16 * NS + tid] = d.depth;
+      cand[17 * NS + tid] = d.s0;
+      cand[18 * NS + tid] = d.s1;
+      cand[19 * NS + tid] = d.s2;
     }
   }
   if (b3d != nullptr) {

@@ -6,6 +6,7 @@
   plan       PlanBase: buffers, the model's weight store, op helpers, launch / hipGraph capture / replay, the f16x2 range guard
   backbones  DLA / VoVNet-V2 / FPN lowering (mixin)
   forward    ForwardPlan (trunk, heads, select / decode / NMS, the exchange record) and DenseDepthPlan
+  losses     LossPlan (trunk, heads, target assignment, loss terms) and assign_targets (DD3D.prepare_targets)
 
 Everything is re-exported here: `from dd3d_amd.engine import ForwardPlan, ConvOp, choose_tiling, ...` keeps working.
 """
@@ -16,3 +17,4 @@ from dd3d_amd.engine.ops import CallOp, ConvOp, FusedStemOp, OpList, SmallcConvO
 from dd3d_amd.engine.plan import HalfRangeOverflow, HalfRangeUnderflow, PlanBase, relax_arithmetic  # noqa: F401
 from dd3d_amd.engine.backbones import BackboneLowering  # noqa: F401
 from dd3d_amd.engine.forward import DenseDepthPlan, ForwardPlan  # noqa: F401
+from dd3d_amd.engine.losses import LossPlan, assign_targets  # noqa: F401

@@ -1,0 +1,303 @@
+"""Loss engine: target assignment and the training loss dict of DD3D / NuscenesDD3D on the MI355X, without gradients.
+
+``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
+runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
+their single-block finalize (FCOS2DLoss fcos2d.py:159-239, FCOS3DLoss fcos3d.py:191-299, NuscenesLoss nuscenes_dd3d.py:199-265).  The
+ground truth of a call is packed into one pinned host mirror and shipped with one asynchronous copy, beside the image metadata.
+
+`assign_targets` is the same assignment kernel on its own, for DD3D.prepare_targets (the reference's call signature).
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from dd3d_amd import hip
+from dd3d_amd.engine.forward import ForwardPlan
+from dd3d_amd.engine.ops import CallOp
+from dd3d_amd.engine.plan import PlanBase
+
+INF = 100000000.0  # prepare_targets.py:8
+LOSS_KEYS_2D = ("loss_cls", "loss_box2d_reg", "loss_centerness")
+# FCOS3DLoss returns its keys in a different order with and without positives (fcos3d.py:217-225 vs :297)
+LOSS_KEYS_3D = ("loss_conf3d", "loss_box3d_quat", "loss_box3d_proj_ctr", "loss_box3d_depth", "loss_box3d_size")
+LOSS_KEYS_3D_EMPTY = ("loss_box3d_quat", "loss_box3d_proj_ctr", "loss_box3d_depth", "loss_box3d_size", "loss_conf3d")
+LOSS_KEYS_NUSC = ("loss_attr", "loss_speed")
+OUT_INDEX = {"loss_cls": 0, "loss_box2d_reg": 1, "loss_centerness": 2, "loss_box3d_quat": 3, "loss_box3d_proj_ctr": 4, "loss_box3d_depth": 5,
+             "loss_box3d_size": 6, "loss_conf3d": 7, "loss_attr": 8, "loss_speed": 9}
+
+
+def loss_keys(box3d, nusc, num_pos):
+    """Keys of the reference's loss dict, in its order (core.py:103-111, nuscenes_dd3d.py:385-397)."""
+    keys = list(LOSS_KEYS_2D)
+    if box3d:
+        keys += LOSS_KEYS_3D if num_pos > 0 else LOSS_KEYS_3D_EMPTY
+    if nusc:
+        keys += LOSS_KEYS_NUSC
+    return keys
+
+
+def feature_locations(h, w, stride, offset="none"):
+    """tridet/utils/tensor2d.py:6-25 compute_features_locations: (x, y), row-major, x fastest."""
+    sx = torch.arange(0, w * stride, step=stride, dtype=torch.float32)
+    sy = torch.arange(0, h * stride, step=stride, dtype=torch.float32)
+    yy, xx = torch.meshgrid(sy, sx, indexing="ij")
+    loc = torch.stack((xx.reshape(-1), yy.reshape(-1)), dim=1)
+    if offset == "half":
+        loc = loc + stride // 2
+    return loc
+
+
+def sizes_of_interest(cfg, num_levels):
+    """prepare_targets.py:19-25: [-1, s0], [s0, s1], ..., [s_last, INF]; one range per level."""
+    soi, prev = [], -1
+    for s in cfg.DD3D.SIZES_OF_INTEREST:
+        soi.append([prev, s])
+        prev = s
+    soi.append([prev, INF])
+    if len(soi) != num_levels:
+        raise ValueError(f"DD3D.SIZES_OF_INTEREST gives {len(soi)} size ranges for {num_levels} feature levels")
+    return soi
+
+
+def check_loss_config(cfg):
+    loc = str(cfg.DD3D.FCOS2D.LOSS.LOC_LOSS_TYPE)
+    if loc != "giou":
+        raise ValueError(f"DD3D.FCOS2D.LOSS.LOC_LOSS_TYPE = {loc!r}: the loss engine implements 'giou' (every reference config's choice) only")
+
+
+def pack_gt(gt_instances, max_gt, box3d, nusc, num_attr, num_classes):
+    """Ground truth of a batch -> (offsets [B + 1] int32, records [n, LOSS_GT_FIELDS] float32) in the layout of dd3d_loss_args.gt.
+    Each instance needs gt_boxes and gt_classes; gt_boxes3d (any object with the reference's Boxes3D fields: quat, proj_ctr, depth,
+    size, inv_intrinsics, which may be float64) when `box3d`; gt_attributes and gt_speeds when `nusc`.  Classes outside
+    [0, num_classes] and attributes outside [0, num_attr] raise ValueError."""
+    off = [0]
+    recs = []
+    for i, inst in enumerate(gt_instances):
+        boxes = inst.gt_boxes.tensor if hasattr(inst.gt_boxes, "tensor") else inst.gt_boxes
+        boxes = torch.as_tensor(boxes).detach().to("cpu", torch.float32).reshape(-1, 4)
+        n = boxes.shape[0]
+        if n > max_gt:
+            raise ValueError(f"image {i} has {n} ground-truth boxes; the loss engine holds at most {max_gt} per image (G_max = {max_gt})")
+        r = np.zeros((n, hip.LOSS_GT_FIELDS), dtype=np.float32)
+        if n:
+            r[:, 0:4] = boxes.numpy()
+            # the kernels index head-map rows and the canonical sizes with these (the reference raises an IndexError on them)
+            cls = torch.as_tensor(inst.gt_classes).to("cpu", torch.int64).reshape(-1)
+            if cls.numel() != n or bool(((cls < 0) | (cls > num_classes)).any()):
+                raise ValueError(f"image {i}: gt_classes must hold {n} values in [0, {num_classes}] ({num_classes} = background)")
+            r[:, 4] = cls.to(torch.int32).numpy().view(np.float32)
+            if nusc:
+                att = torch.as_tensor(inst.gt_attributes).to("cpu", torch.int64).reshape(-1)
+                if att.numel() != n or bool(((att < 0) | (att > num_attr)).any()):
+                    raise ValueError(f"image {i}: gt_attributes must hold {n} values in [0, {num_attr}] ({num_attr} = no attribute)")
+                r[:, 5] = att.to(torch.int32).numpy().view(np.float32)
+                r[:, 6] = torch.as_tensor(inst.gt_speeds).to("cpu", torch.float32).numpy()
+            else:
+                r[:, 5] = np.array([num_attr], dtype=np.int32).view(np.float32)[0]
+                r[:, 6] = np.nan
+            if box3d:
+                b3 = inst.gt_boxes3d
+                f = lambda t, k: torch.as_tensor(t).detach().to("cpu", torch.float32).reshape(n, k).numpy()
+                r[:, 7:11] = f(b3.quat, 4)
+                r[:, 11:13] = f(b3.proj_ctr, 2)
+                r[:, 13:14] = f(b3.depth, 1)
+                r[:, 14:17] = f(b3.size, 3)
+                r[:, 17:26] = f(b3.inv_intrinsics, 9)
+        recs.append(r)
+        off.append(off[-1] + n)
+    return np.asarray(off, dtype=np.int32), (np.concatenate(recs, 0) if recs else np.zeros((0, hip.LOSS_GT_FIELDS), np.float32))
+
+
+class _Targets:
+    """Device buffers of the assignment's outputs for N targets, and the dd3d_loss_args fields that point at them."""
+    def __init__(self, a, N, box3d, nusc, device):
+        self.labels = torch.zeros(N, dtype=torch.int32, device=device)
+        self.target_inds = torch.zeros(N, dtype=torch.int32, device=device)
+        self.box2d_reg = torch.zeros((N, 4), dtype=torch.float32, device=device)
+        self.ctr = torch.zeros(N, dtype=torch.float32, device=device)
+        self.box3d = torch.zeros((N, hip.LOSS_BOX3D_FIELDS), dtype=torch.float32, device=device) if box3d else None
+        self.attributes = torch.zeros(N, dtype=torch.int32, device=device) if nusc else None
+        self.speeds = torch.zeros(N, dtype=torch.float32, device=device) if nusc else None
+        self.flags = torch.zeros(1, dtype=torch.int32, device=device)
+        a.labels, a.target_inds = self.labels.data_ptr(), self.target_inds.data_ptr()
+        a.box2d_reg, a.ctr_target, a.flags = self.box2d_reg.data_ptr(), self.ctr.data_ptr(), self.flags.data_ptr()
+        a.box3d_t = self.box3d.data_ptr() if box3d else None
+        a.attributes = self.attributes.data_ptr() if nusc else None
+        a.speeds = self.speeds.data_ptr() if nusc else None
+
+    def as_dict(self, locations, B, num_levels, level_sizes, num_classes):
+        """The reference's targets dict (prepare_targets.py:65-80, nuscenes_dd3d.py:93-97) as device tensors."""
+        from dd3d_amd.structures import Boxes3D
+        dev = self.labels.device
+        labels = self.labels.long()
+        loc_lv = torch.split(locations, level_sizes)
+        out = {
+            "labels": labels,
+            "box2d_reg_targets": self.box2d_reg,
+            "locations": torch.cat([lv.repeat(B, 1) for lv in loc_lv]),
+            "target_inds": self.target_inds.long(),
+            "im_inds": torch.cat([torch.arange(B, device=dev).repeat_interleave(n) for n in level_sizes]),
+            "fpn_levels": torch.cat([torch.full((B * n, ), l, dtype=torch.long, device=dev) for l, n in enumerate(level_sizes)]),
+            "pos_inds": torch.nonzero(labels != num_classes).squeeze(1),
+        }
+        if self.box3d is not None:
+            t = self.box3d
+            out["box3d_targets"] = Boxes3D(t[:, 0:4], t[:, 4:6], t[:, 6:7], t[:, 7:10], t[:, 10:19].reshape(-1, 3, 3))
+        if self.attributes is not None:
+            out["attributes"] = self.attributes.long()
+            out["speeds"] = self.speeds
+        return out
+
+
+def _fill_common(a, cfg, model, level_hw, strides, B, max_gt):
+    """Geometry, size ranges, centre sampling and the FCOS3D decode / loss settings of dd3d_loss_args."""
+    L = len(level_hw)
+    if L > hip.MAX_LEVELS:
+        raise ValueError(f"{L} feature levels exceed {hip.MAX_LEVELS}")
+    soi = sizes_of_interest(cfg, L)
+    pt = cfg.DD3D.FCOS3D.PREPARE_TARGET
+    off = 0
+    for l, (h, w) in enumerate(level_hw):
+        a.H[l], a.W[l] = int(h), int(w)
+        a.loc_off[l] = off
+        off += int(h) * int(w)
+        a.soi_lo[l], a.soi_hi[l] = float(soi[l][0]), float(soi[l][1])
+        a.radius[l] = float(strides[l] * pt.POS_RADIUS)  # prepare_targets.py:196 (python float, then f32 like the tensor op)
+    a.loc_off[L] = off
+    a.num_levels, a.B, a.num_classes, a.max_gt = L, B, int(model.num_classes), int(max_gt)
+    a.center_sample = int(bool(pt.CENTER_SAMPLE))
+    c3 = cfg.DD3D.FCOS3D
+    a.class_agnostic_3d = int(bool(c3.CLASS_AGNOSTIC_BOX3D))
+    a.scale_depth_by_focal = int(bool(c3.SCALE_DEPTH_BY_FOCAL_LENGTHS))
+    a.allocentric = int(bool(c3.PREDICT_ALLOCENTRIC_ROT))
+    a.depth_is_distance = int(bool(c3.PREDICT_DISTANCE))
+    a.min_depth, a.max_depth, a.focal_factor = float(c3.MIN_DEPTH), float(c3.MAX_DEPTH), float(c3.SCALE_DEPTH_BY_FOCAL_LENGTHS_FACTOR)
+    l2, l3 = cfg.DD3D.FCOS2D.LOSS, c3.LOSS
+    a.focal_alpha, a.focal_gamma = float(l2.ALPHA), float(l2.GAMMA)
+    a.smooth_l1_beta, a.conf3d_temperature = float(l3.SMOOTH_L1_BETA), float(l3.CONF_3D_TEMPERATURE)
+    a.weight_box3d, a.weight_conf3d = float(l3.WEIGHT_BOX3D), float(l3.WEIGHT_CONF3D)
+    nusc = getattr(getattr(cfg.DD3D, "NUSC", None), "LOSS", None)
+    a.weight_attr = float(nusc.WEIGHT_ATTR) if nusc is not None and hasattr(model, "attr_logits") else 0.0
+    a.weight_speed = float(nusc.WEIGHT_SPEED) if nusc is not None and hasattr(model, "attr_logits") else 0.0
+    return off
+
+
+def model_is_nusc(model):
+    return hasattr(model, "attr_logits")
+
+
+def num_attributes(model):
+    return int(model.attr_logits.out_channels) if model_is_nusc(model) else 0
+
+
+def assign_targets(model, locations, gt_instances, feature_shapes, max_gt=hip.LOSS_MAX_GT):
+    """DD3DTargetPreparer.__call__ (prepare_targets.py:28-91) / NuscenesDD3DTargetPreparer.__call__ on the device: one launch of
+    dd3d_loss_assign on the current stream.  `locations`: per-level (H*W, 2) tensors; `feature_shapes`: per-level (H, W)."""
+    cfg, dev = model.cfg, model.device
+    check_loss_config(cfg)
+    level_hw = [(int(s[0]), int(s[1])) for s in feature_shapes]
+    strides = [s.stride for s in model.backbone_output_shape]
+    B = len(gt_instances)
+    box3d, nusc = not model.only_box2d, model_is_nusc(model)
+    a = hip.LossArgs()
+    nloc = _fill_common(a, cfg, model, level_hw, strides, B, max_gt)
+    loc = torch.cat([torch.as_tensor(x).reshape(-1, 2).to(dev, torch.float32) for x in locations]).contiguous()
+    if loc.shape[0] != nloc:
+        raise ValueError(f"{loc.shape[0]} locations for feature shapes {level_hw} ({nloc} locations)")
+    off, recs = pack_gt(gt_instances, max_gt, box3d, nusc, num_attributes(model), int(model.num_classes))
+    gt_off = torch.from_numpy(off).to(dev)
+    gt = torch.from_numpy(recs).to(dev) if recs.shape[0] else torch.zeros((1, hip.LOSS_GT_FIELDS), dtype=torch.float32, device=dev)
+    a.locations, a.gt_off, a.gt = loc.data_ptr(), gt_off.data_ptr(), gt.data_ptr()
+    a.num_attr = num_attributes(model)
+    t = _Targets(a, B * nloc, box3d, nusc, dev)
+    hip.check(hip.lib().dd3d_loss_assign(C.byref(a), hip.current_stream()), "loss_assign")
+    return t.as_dict(loc, B, len(level_hw), [h * w for h, w in level_hw], model.num_classes)
+
+
+class LossPlan(ForwardPlan):
+    """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
+    hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
+    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False):
+        PlanBase.__init__(self, device or model.device, dry_run=dry_run)
+        check_loss_config(model.cfg)
+        from dd3d_amd.engine.tiling import default_tile_policy
+        self.tile_policy = default_tile_policy() or getattr(model, "tile_policy", None) or "latency"  # as ForwardPlan: the forward's own tiles
+        self.exchange, self.camera_sharded, self.has_bev_inputs = False, False, False
+        self.adopt_weight_store(model)
+        self._trunk(model, B, Hp, Wp)
+        self._heads(model, self.features)
+        self._losses(model, max_gt)
+
+    def _losses(self, model, max_gt):
+        cfg, dev, B = model.cfg, self.device, self.B
+        feats = self.features
+        L = len(feats)
+        self.box3d_on, self.nusc = self.b3d_maps is not None, model_is_nusc(model)
+        self.max_gt = int(max_gt)
+        a = hip.LossArgs()
+        level_hw = [(f.H, f.W) for f in feats]
+        self.level_sizes = [h * w for h, w in level_hw]
+        nloc = _fill_common(a, cfg, model, level_hw, self.strides, B, max_gt)
+        off = model.feature_locations_offset
+        self.locations = torch.cat([feature_locations(h, w, self.strides[l], off) for l, (h, w) in enumerate(level_hw)]).to(dev)
+        for l in range(L):
+            a.cls[l] = self.cls_maps[l].t.data_ptr()
+            a.box2d[l] = self.b2d_maps[l].t.data_ptr()
+            a.box3d[l] = self.b3d_maps[l].t.data_ptr() if self.box3d_on else None
+        a.cls_pitch, a.b2d_pitch, a.b3d_pitch = self.cls_pitch, self.b2d_pitch, self.b3d_pitch
+        a.attr_off, a.num_attr, a.speed_off = 0, 0, -1
+        if self.nusc:  # nuScenes extras ride on the cls map (ForwardPlan._heads)
+            a.attr_off, a.num_attr = model.num_classes, num_attributes(model)
+            a.speed_off = model.num_classes + a.num_attr
+        if self.box3d_on:
+            self.canon = torch.tensor([list(r) for r in cfg.DD3D.FCOS3D.CANONICAL_BOX3D_SIZES], dtype=torch.float32, device=dev)
+            a.canon_sizes = self.canon.data_ptr()
+        a.inv_K = self.inv_K.data_ptr()  # written by the trunk's first launch (K^-1 of the images, core.py:93)
+        a.locations = self.locations.data_ptr()
+        # GT staging: [offsets B + 1 (int32), padded to 4 words | records B * max_gt * LOSS_GT_FIELDS], pinned mirror + device twin
+        self.gt_hdr = (B + 1 + 3) // 4 * 4
+        words = self.gt_hdr + B * self.max_gt * hip.LOSS_GT_FIELDS
+        self.host_gt = self.host_buf(words, torch.float32)
+        self.dev_gt = torch.zeros(words, dtype=torch.float32, device=dev)
+        self._gt_words = self.gt_hdr
+        a.gt_off, a.gt = self.dev_gt.data_ptr(), self.dev_gt.data_ptr() + 4 * self.gt_hdr
+        N = B * nloc
+        self.targets = _Targets(a, N, self.box3d_on, self.nusc, dev)
+        nblocks = (N + hip.LOSS_BLOCK - 1) // hip.LOSS_BLOCK
+        self.partials = torch.zeros((nblocks, hip.LOSS_TERMS), dtype=torch.float32, device=dev)
+        self.loss_out = torch.zeros(hip.LOSS_OUT, dtype=torch.float32, device=dev)
+        self.det_count = torch.zeros(1, dtype=torch.int32, device=dev)  # the positive count, in the read-back record
+        a.partials, a.n_partials, a.out, a.num_pos = self.partials.data_ptr(), nblocks, self.loss_out.data_ptr(), self.det_count.data_ptr()
+        self.loss_args = a
+        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_assign(C.byref(a), st), "loss_assign"), "loss_assign",
+                               dict(kind="loss_assign")))
+        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_terms(C.byref(a), st), "loss_terms"), "loss_terms",
+                               dict(kind="loss_terms")))
+
+    def stage_gt(self, gt_instances):
+        """Pack the batch's GT into the pinned mirror (plain host stores); `flush_inputs` ships it."""
+        if len(gt_instances) != self.B:
+            raise ValueError(f"{len(gt_instances)} GT instances for a plan of {self.B} images")
+        off, recs = pack_gt(gt_instances, self.max_gt, self.box3d_on, self.nusc, self.loss_args.num_attr, int(self.model.num_classes))
+        self.inputs_writable()
+        h = self.host_gt.numpy()
+        h[:self.B + 1] = off.view(np.float32)
+        h[self.gt_hdr:self.gt_hdr + recs.size] = recs.reshape(-1)
+        self._gt_words = self.gt_hdr + recs.size
+
+    def flush_inputs(self):
+        """The GT prefix in use goes with the image metadata: one more asynchronous copy per call."""
+        n = self._gt_words
+        self.dev_gt[:n].copy_(self.host_gt[:n], non_blocking=not self.dry_run)
+        super().flush_inputs()
+
+    def loss_dict(self, num_pos):
+        """The reference's loss dict: 0-d float32 device tensors, keys in its order (decided by the positive count)."""
+        vals = self.loss_out.clone()
+        return {k: vals[OUT_INDEX[k]] for k in loss_keys(self.box3d_on, self.nusc, num_pos)}
+
+    def target_dict(self):
+        """The targets of the last run, in the form of DD3D.prepare_targets (copies)."""
+        d = self.targets.as_dict(self.locations, self.B, len(self.features), self.level_sizes, self.model.num_classes)
+        return {k: v.clone() for k, v in d.items()}

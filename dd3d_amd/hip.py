@@ -147,12 +147,35 @@ class NuscMatchArgs(C.Structure):
         ("thr", C.c_double * NUSC_MAX_THRESHOLDS)
     ]
 
+LOSS_GT_FIELDS, LOSS_MAX_GT, LOSS_BOX3D_FIELDS, LOSS_TERMS, LOSS_OUT = 28, 512, 19, 16, 16
+LOSS_BLOCK = 256  # targets per block of dd3d_loss_terms: one partial row per block
+
+
+class LossArgs(C.Structure):
+    """`dd3d_loss_args`."""
+    _fields_ = [
+        ("cls", C.c_void_p * MAX_LEVELS), ("box2d", C.c_void_p * MAX_LEVELS), ("box3d", C.c_void_p * MAX_LEVELS), ("locations", C.c_void_p),
+        ("gt_off", C.c_void_p), ("gt", C.c_void_p), ("inv_K", C.c_void_p), ("canon_sizes", C.c_void_p), ("labels", C.c_void_p),
+        ("target_inds", C.c_void_p), ("box2d_reg", C.c_void_p), ("ctr_target", C.c_void_p), ("box3d_t", C.c_void_p), ("attributes", C.c_void_p),
+        ("speeds", C.c_void_p), ("flags", C.c_void_p), ("partials", C.c_void_p), ("out", C.c_void_p), ("num_pos", C.c_void_p),
+        ("H", C.c_int32 * MAX_LEVELS), ("W", C.c_int32 * MAX_LEVELS), ("loc_off", C.c_int32 * (MAX_LEVELS + 1)),
+        ("soi_lo", C.c_float * MAX_LEVELS), ("soi_hi", C.c_float * MAX_LEVELS), ("radius", C.c_float * MAX_LEVELS),
+        ("num_levels", C.c_int32), ("B", C.c_int32), ("num_classes", C.c_int32), ("max_gt", C.c_int32), ("n_partials", C.c_int32),
+        ("cls_pitch", C.c_int32), ("b2d_pitch", C.c_int32), ("b3d_pitch", C.c_int32), ("attr_off", C.c_int32), ("num_attr", C.c_int32),
+        ("speed_off", C.c_int32), ("center_sample", C.c_int32), ("class_agnostic_3d", C.c_int32), ("scale_depth_by_focal", C.c_int32),
+        ("allocentric", C.c_int32), ("depth_is_distance", C.c_int32), ("min_depth", C.c_float), ("max_depth", C.c_float),
+        ("focal_factor", C.c_float), ("focal_alpha", C.c_float), ("focal_gamma", C.c_float), ("smooth_l1_beta", C.c_float),
+        ("conf3d_temperature", C.c_float), ("weight_box3d", C.c_float), ("weight_conf3d", C.c_float), ("weight_attr", C.c_float),
+        ("weight_speed", C.c_float)
+    ]
+
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
     "dd3d_invert_intrinsics", "dd3d_nms_finalize", "dd3d_bev_nms_aggregate", "dd3d_conv2d_smallc_supported", "dd3d_conv2d_smallc_bf16x3", "dd3d_rotate_iou_eval", "dd3d_d3_box_overlap", "dd3d_image_box_overlap", "dd3d_aligned_bilinear_scale", "dd3d_resize_bilinear_u8",
     "dd3d_format_boxes3d", "dd3d_math_planes", "dd3d_split_planes", "dd3d_maxpool2x2_planes", "dd3d_maxpool2x2_planes_in", "dd3d_upsample2x_add_planes", "dd3d_ese_fused", "dd3d_stem_fused_f16x2", "dd3d_fold_range_flags", "dd3d_pack_readback",
-    "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match"
+    "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match", "dd3d_loss_assign", "dd3d_loss_terms", "dd3d_loss_layout"
 ]
 
 
@@ -220,6 +243,9 @@ def lib():
     L.dd3d_kitti_tp_scores.argtypes = [C.POINTER(KittiMatchArgs), C.c_void_p, C.c_void_p]
     L.dd3d_kitti_pr_counts.argtypes = [C.POINTER(KittiMatchArgs), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.dd3d_nusc_center_match.argtypes = [C.POINTER(NuscMatchArgs), C.c_void_p, C.c_void_p]
+    L.dd3d_loss_assign.argtypes = [C.POINTER(LossArgs), C.c_void_p]
+    L.dd3d_loss_terms.argtypes = [C.POINTER(LossArgs), C.c_void_p]
+    L.dd3d_loss_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

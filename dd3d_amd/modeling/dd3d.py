@@ -2,8 +2,9 @@
 
 Same registered name, constructor signature ``(cfg)``, attributes and call contract as
 tridet/modeling/dd3d/core.py:18-175:  ``model(batched_inputs: List[dict]) -> List[{"instances": Instances}]``.
-Only the inference branch exists here (training is out of scope); everything from the
-uint8 image to the final detections runs in the HIP engine (dd3d_amd.engine) on the model's device.
+Only the inference branch exists as the forward (training is out of scope); everything from the
+uint8 image to the final detections runs in the HIP engine (dd3d_amd.engine) on the model's device.  ``compute_losses`` /
+``prepare_targets`` give the training branch's loss dict and targets without gradients (engine.LossPlan).
 """
 import numpy as np
 import torch
@@ -118,6 +119,19 @@ class DD3D(nn.Module):
         self._evict_plans()
         return plan
 
+    def get_loss_plan(self, B, Hp, Wp):
+        """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans."""
+        from dd3d_amd.engine.losses import LossPlan
+        key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None))
+        plan = self._plans.pop(key, None)
+        if plan is None:
+            plan = LossPlan(self, B, Hp, Wp)
+            if self.use_graph:
+                plan.capture()
+        self._plans[key] = plan
+        self._evict_plans()
+        return plan
+
     def _evict_plans(self):
         """Inputs of ever-changing size would otherwise pin a buffer set (0.5 - 3 GB) per size for the life of the model."""
         while len(self._plans) > max(1, int(self.max_cached_plans)):
@@ -126,6 +140,15 @@ class DD3D(nn.Module):
             self._plans.pop(next(iter(self._plans)))
 
     # ------------------------------------------------------------------ host side of forward
+    def canvas_size(self, batched_inputs):
+        """(B, H, W) of the padded canvas of a batch: ImageList.from_tensors' geometry (image_list.py:120-142), as stage_inputs pads."""
+        sizes = [(int(x["image"].shape[-2]), int(x["image"].shape[-1])) for x in batched_inputs]
+        div = self.backbone.size_divisibility
+        H, W = max(s[0] for s in sizes), max(s[1] for s in sizes)
+        if div > 1:
+            H, W = (H + div - 1) // div * div, (W + div - 1) // div * div
+        return len(sizes), H, W
+
     def stage_inputs(self, batched_inputs, plan=None, first=0, partial=False, flush=True):
         """core.py:65-72: gather images/intrinsics; the padded canvas geometry is ImageList.from_tensors'
         (image_list.py:120-142).  Returns (plan, image_sizes).  `first` (with a fixed `plan` only): the batch goes to positions
@@ -261,6 +284,38 @@ class DD3D(nn.Module):
 
     def _collect_extra(self, r, d, plan):
         pass
+
+    # ------------------------------------------------------------------ training losses (no gradients)
+    @torch.no_grad()
+    def compute_losses(self, batched_inputs):
+        """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
+        each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
+        gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
+        reference: every norm layer uses its running statistics (the head maps are exactly this forward's), one process
+        (reduce_sum is the identity), no gradients."""
+        from dd3d_amd.engine import relax_arithmetic
+        gt = [x["instances"] for x in batched_inputs]
+        while True:
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs))
+            plan.stage_gt(gt)
+            self.stage_inputs(batched_inputs, plan=plan)  # (its flush ships the GT too)
+            plan.run()
+            rb = plan.readback()
+            try:
+                plan.check_status(rb)
+            except FloatingPointError as e:  # the f16x2 range guard, as in forward()
+                if not relax_arithmetic(self, e):
+                    raise
+                continue
+            return plan.loss_dict(int(rb.counts[0]))
+
+    @torch.no_grad()
+    def prepare_targets(self, locations, gt_instances, feature_shapes):
+        """DD3DTargetPreparer.__call__ (prepare_targets.py:28-91; NuscenesDD3D: nuscenes_dd3d.py:29-99) on the device: `locations` per
+        level (H*W, 2), `gt_instances` per image, `feature_shapes` per level (H, W).  Returns the reference's dict of device tensors
+        (box3d_targets as a Boxes3D with float32 K^-1)."""
+        from dd3d_amd.engine.losses import assign_targets
+        return assign_targets(self, locations, gt_instances, feature_shapes)
 
     @torch.no_grad()
     def forward(self, batched_inputs):

@@ -232,6 +232,25 @@ class Boxes3D(GenericBoxes3D):
 
     _FIELDS = ("quat", "proj_ctr", "depth", "size", "inv_intrinsics")
 
+    @classmethod
+    def from_vectors(cls, vecs, intrinsics, device="cpu"):
+        """boxes3d.py:175-218: 10-D vectors [quat wxyz, tvec xyz, size WLH] and the (3, 3) intrinsics -> Boxes3D.  proj_ctr = (K tvec)[:2] /
+        (K tvec)[2] and K^-1 = np.linalg.inv(K) in the input's precision (float64 for the dataset mappers' arrays); K^-1 keeps that dtype."""
+        import numpy as np
+        if len(vecs) == 0:
+            z = lambda k: torch.as_tensor([], dtype=torch.float32, device=device).view(-1, k)
+            return cls(z(4), z(2), z(1), z(3), torch.as_tensor([], dtype=torch.float32, device=device).view(-1, 3, 3))
+        quats, proj_ctrs, depths, sizes = [], [], [], []
+        for vec in vecs:
+            proj_ctr = intrinsics.dot(vec[4:7])
+            quats.append(vec[:4])
+            proj_ctrs.append(proj_ctr[:2] / proj_ctr[-1])
+            depths.append(vec[6:7])
+            sizes.append(vec[7:])
+        f = lambda v: torch.as_tensor(np.asarray(v), dtype=torch.float32, device=device)
+        inv = torch.as_tensor(np.linalg.inv(intrinsics)[None, ...], device=device).expand(len(vecs), 3, 3)
+        return cls(f(quats), f(proj_ctrs), f(depths), f(sizes), inv)
+
     def __getitem__(self, item):
         if isinstance(item, int):
             return Boxes3D(

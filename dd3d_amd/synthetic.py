@@ -111,3 +111,63 @@ def make_inputs(B=1, H=384, W=1280, dataset="kitti", seed=1000, out_hw=None, dev
             d["sample_token"] = f"s{sample}"
         out.append(d)
     return out
+
+
+def make_gt_instances(inputs, num_classes, canonical_sizes, seed=2000, n_per_image=24, empty_images=(), quirk_images=(), num_attributes=None):
+    """Seeded ground truth for `inputs` (make_inputs' batch): per image an ``Instances`` with gt_boxes, gt_classes and gt_boxes3d
+    (built by Boxes3D.from_vectors from float64 intrinsics, as tridet/data/transform_utils.py:116 does) and, with `num_attributes`,
+    gt_attributes / gt_speeds (nuScenes; attribute == num_attributes means "none", some speeds NaN, half of them below 0.08 m/s).  The boxes cover every FPN
+    level's size range, include pairs of equal area and edges on the stride-8 grid (locations exactly on a box edge);
+    `empty_images` get no GT, `quirk_images` a FIRST box with x1 + x2 == 0 (prepare_targets.py:190)."""
+    import numpy as np
+    from dd3d_amd.structures import Boxes, Boxes3D, Instances
+    out = []
+    for i, x in enumerate(inputs):
+        H, W = int(x["image"].shape[-2]), int(x["image"].shape[-1])
+        K = np.asarray(x["intrinsics"], dtype=np.float64)
+        rng = np.random.default_rng(seed + i)
+        n = 0 if i in empty_images else n_per_image
+        boxes = []
+        for j in range(n):
+            side = float(np.exp(rng.uniform(np.log(6.0), np.log(max(H, W) * 1.2))))  # every size range, [-1, 64] .. [512, INF]
+            w, h = side * rng.uniform(0.6, 1.4), side * rng.uniform(0.6, 1.4)
+            cx, cy = rng.uniform(0, W), rng.uniform(0, H)
+            b = [cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2]
+            if j % 4 == 1:  # edges on the location grid
+                b = [float(np.round(v / 8.0) * 8.0) for v in b]
+                if b[2] <= b[0]:
+                    b[2] = b[0] + 8.0
+                if b[3] <= b[1]:
+                    b[3] = b[1] + 8.0
+            if j % 6 == 5 and boxes:  # the same width and height as the previous box, shifted: equal areas on the overlap
+                p = boxes[-1]
+                dx, dy = float(np.round(rng.uniform(-0.3, 0.3) * (p[2] - p[0]))), float(np.round(rng.uniform(-0.3, 0.3) * (p[3] - p[1])))
+                b = [p[0] + dx, p[1] + dy, p[2] + dx, p[3] + dy]
+            boxes.append(b)
+        if n and i in quirk_images:
+            half = (boxes[0][2] - boxes[0][0]) / 2.0
+            boxes[0] = [-half, boxes[0][1], half, boxes[0][3]]
+        boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+        classes = rng.integers(0, num_classes, size=n)
+        vecs = []
+        for j in range(n):
+            q = rng.normal(size=4)
+            q /= np.linalg.norm(q)
+            z = rng.uniform(4.0, 60.0)
+            u, v = (boxes[j, 0] + boxes[j, 2]) / 2.0, (boxes[j, 1] + boxes[j, 3]) / 2.0
+            t = np.linalg.solve(K, np.array([u, v, 1.0])) * z
+            size = np.asarray(canonical_sizes[classes[j]], dtype=np.float64) * rng.uniform(0.7, 1.3, size=3)
+            vecs.append(np.concatenate([q, t, size]))
+        inst = Instances((H, W))
+        inst.gt_boxes = Boxes(torch.from_numpy(boxes))
+        inst.gt_classes = torch.from_numpy(classes.astype(np.int64))
+        inst.gt_boxes3d = Boxes3D.from_vectors(vecs, K)
+        if num_attributes is not None:
+            inst.gt_attributes = torch.from_numpy(rng.integers(0, num_attributes + 1, size=n).astype(np.int64))
+            sp = rng.uniform(0.0, 12.0, size=n).astype(np.float32)
+            slow = rng.uniform(size=n) < 0.5  # slow objects: errors on both sides of the speed loss's beta (0.05) for predictions near 0
+            sp[slow] = rng.uniform(0.0, 0.08, size=int(slow.sum())).astype(np.float32)
+            sp[rng.uniform(size=n) < 0.25] = np.nan
+            inst.gt_speeds = torch.from_numpy(sp)
+        out.append(inst)
+    return out

@@ -600,6 +600,73 @@ typedef struct dd3d_nusc_match_args {  /* host memory */
 } dd3d_nusc_match_args;
 int dd3d_nusc_center_match(const dd3d_nusc_match_args* args, int32_t* match, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training losses of DD3D / NuscenesDD3D without gradients (csrc/losses.hip).
+ * Replaces DD3DTargetPreparer / NuscenesDD3DTargetPreparer (prepare_targets.py:28-235, nuscenes_dd3d.py:24-196), FCOS2DLoss
+ * (fcos2d.py:159-239), FCOS3DLoss (fcos3d.py:191-299), DisentangledBox3DLoss (disentangled_box3d_loss.py) and NuscenesLoss
+ * (nuscenes_dd3d.py:199-265), single process.
+ *
+ * Ground truth: image b owns records gt[gt_off[b] .. gt_off[b+1]) of DD3D_LOSS_GT_FIELDS words, at most max_gt (<= DD3D_LOSS_MAX_GT)
+ * per image: the assignment reads only the first max_gt records of an image (the caller rejects larger images; dd3d_amd raises).
+ * Classes must lie in [0, num_classes] (num_classes = background) and attributes in [0, num_attr]: they index the head-map rows and
+ * the canonical sizes (dd3d_amd checks them before packing):
+ *   0-3 box x1,y1,x2,y2 | 4 class (int bits) | 5 attribute (int bits) | 6 speed | 7-10 quat wxyz | 11-12 proj_ctr | 13 depth
+ *   14-16 size WLH | 17-25 K^-1 row-major | 26-27 unused
+ * Targets are flattened level-first, then image, then H*W (prepare_targets.py:49-63): location n of the N = B * loc_off[L] targets.
+ * `locations` holds the loc_off[L] (x, y) of one image, level-major.
+ *
+ * dd3d_loss_assign: one thread per (image, location), the image's boxes in LDS.  Writes labels (num_classes = background),
+ *   target_inds (-1 for an image without GT), box2d_reg [N][4], ctr_target [N] (0 off the positives), box3d_t [N][19]
+ *   (quat 4, proj_ctr 2, depth 1, size 3, K^-1 9) and, when `attributes` is set, attributes [N] / speeds [N].  With box3d head maps
+ *   it also ORs into flags[0] whether an allocentric decode of a positive is off unit norm (the batch-wide renormalisation of
+ *   geometry.py:48-53, which the loss stage needs before it can decode).
+ * dd3d_loss_terms: one thread per target reads the head maps (layouts of dd3d_select_args), writes per-block partial sums of
+ *   DD3D_LOSS_TERMS terms to `partials` (>= ceil(N / 256) rows), then one single-block launch sums them in a fixed order and writes
+ *   out[DD3D_LOSS_OUT] and num_pos[0].  No float atomics: the result is the same bit for bit on every run.
+ *   out: 0 loss_cls | 1 loss_box2d_reg | 2 loss_centerness | 3 loss_box3d_quat | 4 loss_box3d_proj_ctr | 5 loss_box3d_depth
+ *        6 loss_box3d_size | 7 loss_conf3d | 8 loss_attr | 9 loss_speed | 10 num_pos | 11 loss_denom | 12-15 unused
+ * dd3d_loss_layout: sizeof(dd3d_loss_args) and the byte offsets of its fields (layout check of the bindings; host only).
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_LOSS_GT_FIELDS 28
+#define DD3D_LOSS_MAX_GT 512
+#define DD3D_LOSS_BOX3D_FIELDS 19
+#define DD3D_LOSS_TERMS 16
+#define DD3D_LOSS_OUT 16
+typedef struct dd3d_loss_args {  /* host memory */
+  const float* cls[DD3D_MAX_LEVELS];   /* head maps, device (dd3d_loss_assign: may be NULL) */
+  const float* box2d[DD3D_MAX_LEVELS];
+  const float* box3d[DD3D_MAX_LEVELS]; /* NULL entries => 2D only */
+  const float* locations;              /* [loc_off[num_levels]][2] */
+  const int32_t* gt_off;               /* [B + 1] */
+  const float* gt;                     /* [gt_off[B]][DD3D_LOSS_GT_FIELDS] */
+  const float* inv_K;                  /* [B][9] K^-1 of the images (the prediction decode) */
+  const float* canon_sizes;            /* [num_classes][3] */
+  int32_t* labels;
+  int32_t* target_inds;
+  float* box2d_reg;
+  float* ctr_target;
+  float* box3d_t;                      /* [N][DD3D_LOSS_BOX3D_FIELDS] or NULL */
+  int32_t* attributes;                 /* nuScenes targets or NULL */
+  float* speeds;
+  int32_t* flags;                      /* [1] */
+  float* partials;                     /* [n_partials][DD3D_LOSS_TERMS] */
+  float* out;                          /* [DD3D_LOSS_OUT] */
+  int32_t* num_pos;                    /* [1] */
+  int32_t H[DD3D_MAX_LEVELS], W[DD3D_MAX_LEVELS];
+  int32_t loc_off[DD3D_MAX_LEVELS + 1];
+  float soi_lo[DD3D_MAX_LEVELS], soi_hi[DD3D_MAX_LEVELS]; /* sizes of interest, both ends inclusive */
+  float radius[DD3D_MAX_LEVELS];       /* stride * POS_RADIUS */
+  int32_t num_levels, B, num_classes, max_gt, n_partials;
+  int32_t cls_pitch, b2d_pitch, b3d_pitch, attr_off, num_attr, speed_off;
+  int32_t center_sample, class_agnostic_3d, scale_depth_by_focal, allocentric, depth_is_distance;
+  float min_depth, max_depth, focal_factor;
+  float focal_alpha, focal_gamma, smooth_l1_beta, conf3d_temperature;
+  float weight_box3d, weight_conf3d, weight_attr, weight_speed;
+} dd3d_loss_args;
+int dd3d_loss_assign(const dd3d_loss_args* args, void* stream);
+int dd3d_loss_terms(const dd3d_loss_args* args, void* stream);
+int dd3d_loss_layout(int64_t* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
