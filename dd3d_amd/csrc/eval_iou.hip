@@ -6,7 +6,15 @@
 //   d3_overlap_kernel        d3_box_overlap_kernel :330-357
 //   image_overlap_kernel     image_box_overlap :360-381
 // One lane per (box, query) pair, 64x4 pairs per block, query boxes of the block's columns in LDS.  float32 throughout, in the
-// reference's operation order (fp contraction off), so results agree with it to rounding of cos / sin / sqrt.
+// reference's operation order (fp contraction off).  What that buys, and what it does not:
+//   - the only inputs that can differ from the reference's run are the last bits of cos / sin.  Where the reference's algorithm is
+//     itself stable against such a bit (tests/eval_overlap_cases.py `stable`: every family of box pairs an evaluation is made of --
+//     near pairs, identical, nested, axis-aligned, touching, far range), the kernel is within 1e-4 of the smaller box's area of the
+//     CPU oracle and within E_FAMILY + 1e-4 (7e-6 .. 6e-4, measured per family there) of a float64 clipping of the same boxes;
+//   - for nearly parallel, nearly coincident edges (the same box turned by 1e-7 .. 1e-3 rad, a shared edge at a general yaw) the
+//     reference's crossing point is Cramer's rule with a vanishing determinant: its own result is wrong by up to tens of box areas
+//     and flips with the last bit of the trigonometry.  This kernel restates that behaviour on purpose and promises nothing there
+//     beyond a finite-or-NaN value in every element; DESIGN.md has the measured shares.
 #include "common.h"
 
 DD3D_NOTE_BUILD_FLAGS
@@ -20,7 +28,10 @@ struct P2 {
 };
 
 __device__ __forceinline__ void rbox_corners(const float* b, P2* c) {
-  const float a_cos = cosf(b[4]), a_sin = sinf(b[4]);
+  // cos / sin are formed in float64 and rounded once: the correctly rounded float32 values, independent of the device's math
+  // library.  cosf / sinf may be one float32 step off, and on a few pairs that step alone moves the intersection by close to 1e-4 of
+  // the box area (tests/eval_overlap_cases.py, `stable`); with this the kernel repeats the CPU oracle's arithmetic bit for bit.
+  const float a_cos = (float)cos((double)b[4]), a_sin = (float)sin((double)b[4]);
   const float hx = b[2] / 2.f, hy = b[3] / 2.f;
   const float sx[4] = {-hx, -hx, hx, hx}, sy[4] = {-hy, hy, hy, -hy};
 #pragma unroll

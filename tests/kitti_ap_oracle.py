@@ -57,10 +57,12 @@ def clean_kitti_data(gt_anno, dt_anno, current_class, difficulty, id_to_name, pa
     return num_valid, ignored_gt, ignored_dt, dontcare
 
 
-def tp_scores(overlaps, scores, ignored_gt, ignored_dt, min_overlap):
-    """Pass 1 of one image: the scores of the detections matched to valid GT, GT order.  overlaps[det][gt] (float64)."""
+def tp_scores(overlaps, scores, ignored_gt, ignored_dt, min_overlap, per_gt=False):
+    """Pass 1 of one image: the scores of the detections matched to valid GT, GT order.  overlaps[det][gt] (float64).
+    With `per_gt` the same scores are returned at their GT's index in a list of len(ignored_gt), -inf at every other GT (the
+    layout of `dd3d_kitti_tp_scores`)."""
     assigned = [False] * len(scores)
-    out = []
+    out = [-np.inf] * len(ignored_gt) if per_gt else []
     for g in range(len(ignored_gt)):
         if ignored_gt[g] == -1:
             continue
@@ -74,7 +76,10 @@ def tp_scores(overlaps, scores, ignored_gt, ignored_dt, min_overlap):
             continue  # (a miss; pass 1 does not count it)
         assigned[pick] = True
         if not (ignored_gt[g] == 1 or ignored_dt[pick] == 1):
-            out.append(scores[pick])
+            if per_gt:
+                out[g] = scores[pick]
+            else:
+                out.append(scores[pick])
     return out
 
 

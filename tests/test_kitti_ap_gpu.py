@@ -1,6 +1,7 @@
 """KITTI AP engine on the MI355X against the reference's own results (tests/golden/kitti_ap.npz): the two HIP passes fed the
 reference's overlaps, the engine end to end on HIP overlaps, KITTI3DEvaluator.process + evaluate, a 500-image KITTI-shaped set
-against the plain-Python oracle, and the distributed gather (gloo, two ranks on the one GPU)."""
+against the plain-Python oracle (one slot), a 320-image set with up to 100 and three times 390 detections per image against the
+oracle in every slot of both metrics, and the distributed gather (gloo, two ranks on the one GPU)."""
 import json
 import multiprocessing as mp
 import os
@@ -101,8 +102,9 @@ def test_evaluator_process_evaluate_matches_reference(golden, tmp_path, hiplib):
     assert open(os.path.join(sub, "000000.txt")).read() == str(golden["ev_submission_000000"])
 
 
-def _kitti_shaped(rng, n_img, n_gt=8, n_dt=40):
-    """KITTI-val-shaped synthetic set: ~n_gt GT (with Van / Person_sitting / DontCare) and up to n_dt detections per image."""
+def _kitti_shaped(rng, n_img, n_gt=8, n_dt=40, fixed_dt=None):
+    """KITTI-val-shaped synthetic set: ~n_gt GT (with Van / Person_sitting / DontCare) and up to n_dt (or exactly fixed_dt)
+    detections per image."""
     types = ["Car", "Car", "Van", "Pedestrian", "Person_sitting", "Cyclist", "Truck", "DontCare"]
     gts, dts = [], []
     for _ in range(n_img):
@@ -114,7 +116,7 @@ def _kitti_shaped(rng, n_img, n_gt=8, n_dt=40):
                       rng.uniform(1.4, 1.8), rng.uniform(1.5, 1.9), rng.uniform(3.5, 4.5), rng.uniform(-10, 10), rng.uniform(1, 2), rng.uniform(5, 45),
                       rng.uniform(-3, 3)])
         d = []
-        for _ in range(int(rng.integers(0, n_dt + 1))):
+        for _ in range(fixed_dt if fixed_dt is not None else int(rng.integers(0, n_dt + 1))):
             src = g[int(rng.integers(0, len(g)))] if g and rng.random() < 0.7 else None
             loc = (np.array(src[11:14]) + rng.normal(0, 0.3, 3)) if src else np.array([rng.uniform(-10, 10), rng.uniform(1, 2), rng.uniform(5, 45)])
             box = (np.array(src[4:8]) + rng.normal(0, 3, 4)) if src else np.array([10.0, 150.0, 60.0, 150 + rng.uniform(10, 100)])
@@ -151,6 +153,52 @@ def test_500_images_counts_match_oracle_on_hip_overlaps(hiplib):
             for i, x in enumerate(cleaned):
                 want[t] += O.pr_counts(blocks[i], dt[i]["score"], x[1], x[2], THRESHOLDS[o], thr)
         assert np.array_equal(counts[cd, o, :len(want_th)], want)
+
+
+def test_all_slots_match_oracle_at_topk_and_tta_shapes(hiplib):
+    """Up to 100 detections per image (POST_NMS_TOPK) and three images with 390 (the merged TTA detections), so that the matching
+    kernels run several chunks per lane in the engine too; 320 images are 50 shards of six and a remainder shard of 20.  Every one
+    of the 15 x 2 (class x difficulty, overlap) slots of both metrics is compared: true-positive scores, thresholds, every count,
+    and the final dictionary, against the plain-Python oracle run on the HIP overlaps read back."""
+    from dd3d_amd.evaluators import KITTIEvaluationEngine
+    rng = np.random.default_rng(390)
+    n_img = 320
+    gf, df = _kitti_shaped(rng, n_img, n_dt=100)
+    for i in (10, 161, 319):
+        g1, d1 = _kitti_shaped(rng, 1, n_gt=10, fixed_dt=390)
+        gf[i], df[i] = g1[0], d1[0]
+    gt = [KITTIEvaluationEngine._format(i, f, False) for i, f in enumerate(gf)]
+    dt = [KITTIEvaluationEngine._format(i, f, True) for i, f in enumerate(df)]
+    eng = KITTIEvaluationEngine(ID_TO_NAME)
+    p = eng._prepare(gt, dt, THRESHOLDS)
+    assert len(p.shards) == 51 and p.shards[-1][1] - p.shards[-1][0] == 20 and p.max_dt == 390 and (p.nd > 64).sum() > 80
+    n_o = len(THRESHOLDS)
+    ap = {}
+    for metric in ("BOX3D_AP", "BEV_AP"):
+        ov = eng._overlap_blocks(p, metric, torch.device("cuda"))
+        tps = eng._tp_scores(p, ov)
+        ths = eng._thresholds(p, tps)
+        counts = eng._pr_counts(p, ov, ths)
+        host = ov.cpu().numpy().astype(np.float64)
+        blocks = [host[p.ov_off[i]:p.ov_off[i + 1]].reshape(p.nd[i], p.ng[i]) for i in range(n_img)]
+        want = O.eval_metric_counts(blocks, gt, dt, ID_TO_NAME, THRESHOLDS)
+        curves = 0
+        for c in range(len(CLASSES)):
+            for d in range(3):
+                for o in range(n_o):
+                    cd, slot = c * 3 + d, (c, d, o)
+                    got_tp = tps[cd, o][tps[cd, o] != -np.inf]
+                    assert got_tp.tolist() == [s for q in want["tp_scores"][slot] for s in q], (metric, slot)
+                    assert ths[cd * n_o + o] == want["thresholds"][slot], (metric, slot)
+                    n = len(want["thresholds"][slot])
+                    assert np.array_equal(counts[cd, o, :n], want["counts"][slot]) and not counts[cd, o, n:].any(), (metric, slot)
+                    curves += n >= 5
+        assert curves >= 10  # a third of the slots have real curves
+        recall, precision = eng._curves(p, ths, counts)
+        assert np.array_equal(recall, want["recall"], equal_nan=True) and np.array_equal(precision, want["precision"], equal_nan=True)
+        ap[metric] = O.mean_ap(want["precision"], want["recall"])
+    expect = O.results(ap["BOX3D_AP"], ap["BEV_AP"], ID_TO_NAME, THRESHOLDS)
+    same_dict(KITTIEvaluationEngine(ID_TO_NAME).evaluate(gt, dt, THRESHOLDS), list(expect.keys()), np.array([float(v) for v in expect.values()]))
 
 
 def _rank_main(rank, init_file, golden_path, out_dir):
