@@ -103,7 +103,17 @@ __global__ __launch_bounds__(256) void aligned_bilinear_scale_kernel(const float
     const int y = (int)(t % H);
     const int b = (int)(t / H);
     const int ys = half ? max(y - f / 2, 0) : y, xs = half ? max(x - f / 2, 0) : x;
-    const float ry = scale * (float)ys, rx = scale_w * (float)xs;
+    float ry, rx;
+    {
+      // The source coordinate is ROUNDED to f32 before its fraction is taken, as in the reference (upsample_bilinear2d computes the index in
+      // the map's scalar type).  Left to itself the compiler fuses the product into `ry - y0` (one fma, the product unrounded): a fraction
+      // that differs from the reference's by up to an ulp of the coordinate, i.e. by 6e-5 at column 800 for a factor that is no power of two.
+      // (The pragma is honoured under hipcc's default -ffp-contract=fast-honor-pragmas; a build with plain -ffp-contract=fast would ignore it,
+      // and tests/test_glue_kernels_gpu.py section D would say so.)
+#pragma clang fp contract(off)
+      ry = scale * (float)ys;
+      rx = scale_w * (float)xs;
+    }
     const int y0 = (int)ry, x0 = (int)rx;
     const float ly = ry - (float)y0, lx = rx - (float)x0;
     const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);  // row / column h, w of the padded map replicate h-1, w-1
