@@ -177,13 +177,14 @@ __device__ __forceinline__ void split_pack(float x0, float x1, unsigned (&w)[Pla
   }
 }
 
-// MODE == DD3D_MATH_F32: f32 NHWC store only (the kernel's math mode has no planes).
-// WM x WN: the block's wave grid (only the range-guard sample needs it; 1 x 1 = every wave is "the" wave of its block).
-template <int TM, int TN, int MODE = DD3D_MATH_F32, int WM = 1, int WN = 1>
+// Pixel-per-register form, for the kernels of conv_igemm.hip (the split-plane kernels use conv_epilogue_t below).
+// MODE == DD3D_MATH_F32: f32 NHWC store only (the kernel's math mode has no planes); DD3D_MATH_BF16X3: f32 NHWC and / or split planes.
+template <int TM, int TN, int MODE = DD3D_MATH_F32>
 __device__ __forceinline__ void conv_epilogue(const ConvKArgs& a, const dd3d_conv_seg& s, const f32x16 (&acc)[TM][TN], int m0, int n0,
                                               int wm, int wn, int lane) {
   const gcfp g_res = as_g(s.res);
   const gfp g_out = as_g(s.out);
+  static_assert(!Planes<MODE>::F16, "the half-precision planes (plane scale, range guard) are written by conv_epilogue_t only");
   const int nlim = s.n_limit > 0 ? s.n_limit : a.N;
   if constexpr (MODE == DD3D_MATH_F32) {
 #pragma unroll
@@ -219,17 +220,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& a, const dd3d_con
     const bool w32 = s.out != nullptr, wpl = s.out_planes != nullptr;
     const long cstride = (long)s.M * (NP * 64);  // bytes per 32-channel chunk image of the output
     const int odd = lane & 1;
-    const float pscale = a.out_plane_scale;
-    int ovf = 0;
-    float amx = 0.f;  // F16X2: largest |scaled value| this lane stores as planes (tracked by the block's reporting wave only, see below)
-    // The reporting wave of the block: chosen from the TILE's coordinates (not the block index: with split-K the block that finishes a tile
-    // is whichever slice arrives last), rotating over the wave grid, and moved to wave row / column 0 when the chosen one holds only rows
-    // >= M or columns >= N (row m0 and column n0 of a tile are always real) -- wave-uniform.
-    const int seed = m0 / (TM * 32 * WM) + n0 / (TN * 32 * WN);
-    int wm_sel = seed % WM, wn_sel = (seed / WM) % WN;
-    if (m0 + wm_sel * TM * 32 >= s.M) wm_sel = 0;
-    if (n0 + wn_sel * TN * 32 >= nlim) wn_sel = 0;
-    const bool report = Planes<MODE>::F16 && a.amax != nullptr && wm == wm_sel && wn == wn_sel;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int nb = n0 + (wn * TN + j) * 32;  // wave-uniform: first channel of this column block
@@ -271,12 +261,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& a, const dd3d_con
             const float own = odd ? v[rb] : v[ra];
             const int m = mb + (odd ? (rb & 3) + 8 * (rb >> 2) : (ra & 3) + 8 * (ra >> 2));
             unsigned w[NP];
-            float e0 = odd ? recv : own, e1 = odd ? own : recv;
-            if constexpr (Planes<MODE>::F16) {
-              e0 *= pscale, e1 *= pscale;
-              ovf |= !(fabsf(e0) <= 65504.f) | !(fabsf(e1) <= 65504.f);
-              if (report && m < s.M) amx = fmaxf(amx, fmaxf(fabsf(e0), fabsf(e1)));
-            }
+            const float e0 = odd ? recv : own, e1 = odd ? own : recv;
             split_pack<MODE>(e0, e1, w);
             if (m < s.M) {
               const gbp dst = pl_base + (long)m * (NP * 64);
@@ -285,19 +270,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& a, const dd3d_con
             }
           }
         }
-      }
-    }
-    if constexpr (Planes<MODE>::F16) {
-      if (ovf && a.status) atomicOr(a.status, DD3D_STATUS_F16_OVERFLOW);  // (NaN / inf inputs trip it as well)
-      // Underflow side of the range guard: a SAMPLE of the stored outputs -- one wave tile per block, the wave rotating with the tile's
-      // coordinates so that every (row, column) sub-tile position is covered -- is folded into one of 16 per-launch maxima (128 B apart:
-      // different L2 lines).  Every wave of every block reporting into ONE address cost 16 % of the whole forward (2016 same-address
-      // atomics at the end of a 100 us launch, measured: profiles/r03g_amax_ab.txt); the sample is a lower bound of the true maximum,
-      // so a tensor that passes the guard on it passes on all of its entries.
-      if (report) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) amx = fmaxf(amx, __shfl_xor(amx, d, 64));
-        if (lane == 0 && amx > 0.f) atomicMax(reinterpret_cast<unsigned*>(a.amax + (seed & 15) * 32), __float_as_uint(amx));
       }
     }
   }
@@ -309,12 +281,12 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& a, const dd3d_con
 // rows of every 32-row block are laid into LDS in the order chan_of_row() -- the LDS-DMA's per-lane source address, nothing else -- so
 // that those 16 channels are CONSECUTIVE: half-wave h = lane >> 5 owns channels 16 h .. 16 h + 15 of the block, register r = channel
 // 16 h + r.  Every memory instruction of the epilogue is then 16 bytes per lane on consecutive channels of one pixel:
-//   f32 NHWC store 4 x dwordx4 per block (the pixel-per-register form: 16 x dword), split-plane store 2 x dwordx4 per plane (16 x dword
+//   f32 NHWC store 4 x dwordx4 per block (the pixel-per-register form, conv_epilogue: 16 x dword), split-plane store 2 x dwordx4 per plane (16 x dword
 //   + 8 DPP swaps for two planes), residual 4 x dwordx4 (16 x dword).
 // The epilogue of a short-K convolution is bound by the NUMBER of memory instructions its CU must issue (~70-80 cycles each whatever
 // their width, MI355X_MICROARCH.md "store-ISSUE-bound"): DLA level 2 (K = 576) spent 96 of them per wave against a 5.8 us K loop.
 // The per-channel vectors (scale, bias, lower clamp with the ReLU folded in) of the block's BN columns are staged in LDS by the
-// kernel's prologue (epi_stage_vectors: global loads issued before the first LDS-DMA, written to LDS after the prologue's barrier), so
+// kernel's prologue (epi_load_vectors / epi_store_vectors: global loads issued before the first LDS-DMA, written to LDS after the prologue's barrier), so
 // the epilogue reads them with ds_read_b128 -- no vector-memory load sits between the stores of consecutive blocks.
 // Residual sources (dd3d_conv_seg.res_mode): 1 f32 NHWC same pixel; 2 split planes, same pixel; 3 split planes of the map at HALF the
 // resolution (nearest-neighbour x2 upsampling fused into the add: the FPN top-down path).
@@ -391,7 +363,9 @@ __device__ __forceinline__ void conv_epilogue_t(const ConvKArgs& a, const dd3d_c
   constexpr int NP = Planes<MODE>::NP;
   constexpr int BN = TN * 32 * WN;
   constexpr bool RES = epi_residual_ok<TM, TN, WM, WN>();
-  // `scratch` (DD3D_EPI_LDS): this wave's private NP * 2 KiB of LDS.  The split planes of a 32 x 32 accumulator block are ONE contiguous
+  // `scratch`: this wave's private NP * 2 KiB of LDS, non-null exactly when the segment has split-plane output (s.out_planes; both kernels
+  // pass it that way, so the store straight from the registers below never runs.  The compiler cannot see that and keeps its code: taking
+  // the branch out changes the machine code of every instantiation, which needs a measurement of its own).  The split planes of a 32 x 32 accumulator block are ONE contiguous
   // run of memory, [pixel][plane][64 B] -- 32 pixels x NP x 64 B -- but a lane holds a pixel's HALF rows (32 bytes per plane).  Stored
   // straight from the registers, an instruction writes 64 scattered 16-byte pieces (two per 64-byte row: twice the write requests, all
   // of them partial lines).  Staged through LDS in the memory layout (16-byte units XOR-swizzled so that both sides are conflict-free)
@@ -407,8 +381,15 @@ __device__ __forceinline__ void conv_epilogue_t(const ConvKArgs& a, const dd3d_c
   const int rmode = RES ? s.res_mode : 0;
   const long res_cstride = rmode == 3 ? (long)s.B * (s.Ho >> 1) * (s.Wo >> 1) * (NP * 64) : cstride;
   int ovf = 0;
-  float amx = 0.f;
-  // the reporting wave of the block (range-guard sample): see conv_epilogue
+  float amx = 0.f;  // F16X2: largest |scaled value| this lane stores as planes (tracked by the block's reporting wave only)
+  // Range guard of the half-precision planes.  Overflow: every stored value is checked (ovf).  Underflow: a SAMPLE of the stored outputs --
+  // one wave tile per block, the wave rotating with the tile's coordinates so that every (row, column) sub-tile position is covered -- is
+  // folded into one of 16 per-launch maxima (128 B apart: different L2 lines).  Every wave of every block reporting into ONE address cost
+  // 16 % of the whole forward (2016 same-address atomics at the end of a 100 us launch, measured: profiles/r03g_amax_ab.txt); the sample is
+  // a lower bound of the true maximum, so a tensor that passes the guard on it passes on all of its entries.
+  // The reporting wave of the block: chosen from the TILE's coordinates (not the block index: with split-K the block that finishes a tile
+  // is whichever slice arrives last), rotating over the wave grid, and moved to wave row / column 0 when the chosen one holds only rows
+  // >= M or columns >= N (row m0 and column n0 of a tile are always real) -- wave-uniform.
   const int seed = m0 / (TM * 32 * WM) + n0 / (TN * 32 * WN);
   int wm_sel = seed % WM, wn_sel = (seed / WM) % WN;
   if (m0 + wm_sel * TM * 32 >= s.M) wm_sel = 0;

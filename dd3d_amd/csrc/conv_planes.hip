@@ -1,5 +1,5 @@
 // Implicit-GEMM convolution for gfx950 whose INPUT is already split into 16-bit planes (the producer's epilogue wrote them,
-// conv_common.h::conv_epilogue): f32-equivalent (three bf16 terms, six cross products) or reduced (two terms / one term) products
+// conv_common.h::conv_epilogue_t): f32-equivalent (three bf16 terms, six cross products) or reduced (two terms / one term) products
 // on the bf16 matrix pipe with NO VALU work in the main loop.
 //
 //   A  activations  [chunk c/32][pixel (b, h, w)][plane][32]   16-bit terms, written by the previous layer
@@ -24,63 +24,25 @@ DD3D_NOTE_BUILD_FLAGS
 
 namespace dd3d {
 
-// Scheduling pattern of one phase: NMFMA matrix instructions, NDMA LDS-DMA issues and NDS fragment reads in ONE region.  The DMAs go
-// first (longest latency), one per MFMA; then one ds_read per MFMA; the remaining MFMAs close the phase.  Without it the machine
-// scheduler sinks the reads to just before their first use in the NEXT phase and serialises read -> wait -> MFMA.
-template <int NMFMA, int NDS, int NDMA>
-__device__ __forceinline__ void sched_interleave() {
-  constexpr int NPAIR = NDMA + NDS < NMFMA ? NDMA + NDS : NMFMA;
-#pragma unroll
-  for (int i = 0; i < NPAIR; ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-    if (i < NDMA) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);  // one VMEM (the LDS-DMA)
-    else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);           // one DS read
-  }
-  if constexpr (NDMA + NDS > NPAIR) {
-    __builtin_amdgcn_sched_group_barrier(0x010, NDMA > NPAIR ? NDMA - NPAIR : 0, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, NDMA > NPAIR ? NDS : NDMA + NDS - NPAIR, 0);
-  }
-  if constexpr (NMFMA > NPAIR) __builtin_amdgcn_sched_group_barrier(0x008, NMFMA - NPAIR, 0);
-}
-
-#ifndef DD3D_PREFETCH_DISTANCE
-#define DD3D_PREFETCH_DISTANCE 0  // K-tiles between the L2 touch of a tile and its DMA (0: no touch).  Measured: the touches only add VMEM instructions (towers 110 -> 115 us, small convs 22 -> 31 us): the loop is bound by DMA instruction throughput, not by miss latency
-#endif
-#ifndef DD3D_PRODUCER_WAVES
-#define DD3D_PRODUCER_WAVES 0  // loader waves of the warp-specialised form (0: every wave loads and computes)
-#endif
 #ifndef DD3D_LDS_KIB_8W
 #define DD3D_LDS_KIB_8W 144
 #endif
 #ifndef DD3D_LDS_KIB_4W
 #define DD3D_LDS_KIB_4W 72
 #endif
-#ifndef DD3D_EPI_LDS
-#define DD3D_EPI_LDS 1  // 1: the transposed epilogue stages its plane stores through LDS (1 KiB of consecutive bytes per store instruction); 0: straight from the registers (A/B)
-#endif
-#ifndef DD3D_EPI_T
-#define DD3D_EPI_T 1  // 1: transposed accumulators + the 16-bytes-per-lane epilogue (conv_common.h::conv_epilogue_t); 0: round-3 form (A/B)
-#endif
-#ifndef DD3D_SCHED_VARIANT
-#define DD3D_SCHED_VARIANT 1  // 0: DMA burst right after the barrier; 1: evenly spread over the phase; 2: spread over both phases of a step (NS >= 3)
-#endif
-
-// PW > 0: warp-specialised form -- PW extra LOADER waves (one per SIMD) issue every LDS-DMA of the block and the WM x WN compute waves
-// only read fragments and issue MFMAs.  An LDS-DMA instruction holds its wave's issue slot for ~60-180 cycles (address path), and in
-// the unspecialised loop all waves pay that at the same moment (right after the barrier): measured on the head towers, DMA-only loop
-// 55 us, MFMA-only loop 65 us, both in every wave 82 us (zero operands).  Loaders and compute waves meet at the same one barrier per K-tile.
-template <int TM, int TN, int WM, int WN, int NS, int MODE, bool SK, int PW = 0>
-__global__ __launch_bounds__(64 * (WM * WN + PW)) void conv_igemm_planes_kernel(const ConvKArgs a) {
+// (The trailing int is always 0: it counted the loader waves of a warp-specialised form that is gone, and stays because the kernel's name --
+// the key of the committed profiles -- spells it out.)
+template <int TM, int TN, int WM, int WN, int NS, int MODE, bool SK, int = 0>
+__global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_kernel(const ConvKArgs a) {
   constexpr int NP = Planes<MODE>::NP;
   constexpr int BM = TM * 32 * WM;
   constexpr int BN = TN * 32 * WN;
   constexpr int NW = WM * WN;
-  constexpr int NTHR = 64 * NW;      // compute threads (the accumulator / split-K layouts are theirs)
-  constexpr int NL = PW > 0 ? PW : NW;  // waves that issue DMA
+  constexpr int NTHR = 64 * NW;
   constexpr int PLA = BM * 64, PLB = BN * 64;      // bytes per plane of a stage
   constexpr int A_BYTES = NP * PLA, STAGE = NP * (PLA + PLB);
   constexpr int RA = BM / 16, RB = BN / 16;        // 16-row blocks (one 1-KiB DMA piece per plane)
-  constexpr int QN = (RA + RB + NL - 1) / NL;      // row blocks per loading wave (the surplus re-fetches the last block)
+  constexpr int QN = (RA + RB + NW - 1) / NW;      // row blocks per wave (the surplus re-fetches the last block)
   constexpr int P = QN * NP;                       // DMA instructions per wave and K-tile
   constexpr int EV_OFF = NS * STAGE;  // [scale | bias | lo][BN] floats of the epilogue (conv_epilogue_t)
   static_assert(NS >= 2 && EV_OFF + 12 * BN <= 160 * 1024, "LDS ring");
@@ -91,8 +53,8 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void conv_igemm_planes_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool loader = PW > 0 && wave >= NW;          // wave-uniform role
-  const int lw = PW > 0 ? (wave >= NW ? wave - NW : 0) : wave;  // index among the loading waves
+  // (wave < NW always: a clamp left from the loader waves.  Dropping it re-allocates the registers of every instantiation, so it goes with
+  // the next change that is measured on the GPU anyway, not with a deletion that promises the same machine code.)
   const int wm = (wave < NW ? wave : 0) / WN;
   const int wn = (wave < NW ? wave : 0) - wm * WN;
 
@@ -131,7 +93,7 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void conv_igemm_planes_kernel(
     const int howo = s.Ho * s.Wo;
 #pragma unroll
     for (int q = 0; q < QN; ++q) {
-      const int r = min(q * NL + lw, RA + RB - 1);
+      const int r = min(q * NW + wave, RA + RB - 1);
       q_isA[q] = r < RA;
       q_dst[q] = r < RA ? r * 1024 : A_BYTES + (r - RA) * 1024;
       q_pst[q] = r < RA ? PLA : PLB;
@@ -145,12 +107,9 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void conv_igemm_planes_kernel(
       const int hi0 = ho * a.stride - a.pad, wi0 = wo * a.stride - a.pad;
       const long a_off = (((long)b * s.H + hi0) * s.W + wi0) * (NP * 64) + slot16;
       // B geometry (rows past Npad feed columns >= N, which are never stored)
-#if DD3D_EPI_T  // LDS row R of the B rows holds filter row chan_of_row(R) of its 32-row block (conv_common.h::conv_epilogue_t)
+      // LDS row R of the B rows holds filter row chan_of_row(R) of its 32-row block (conv_common.h::conv_epilogue_t)
       const int brow = (r - RA) * 16 + (lane >> 2);
       const int n = min(n0 + (brow & ~31) + chan_of_row(brow & 31), a.Npad - 1);
-#else
-      const int n = min(n0 + (r - RA) * 16 + (lane >> 2), a.Npad - 1);
-#endif
       const long b_off = (long)n * nk * (NP * 64) + slot16;
       a_hi0[q] = r < RA ? (live ? hi0 : -(1 << 28)) : 0;  // dead A rows are never inside [0, H); B rows always are
       a_wi0[q] = r < RA ? wi0 : 0;
@@ -159,7 +118,7 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void conv_igemm_planes_kernel(
   }
 
   // The stream walks this block's K-tiles in order; (chunk, tap) are carried instead of divided out of kt.  Tiles past the end
-  // re-fetch the last one (into a stage nobody reads any more): every issue_tile() is exactly P DMA instructions, so the counted
+  // re-fetch the last one (into a stage nobody reads any more): every emit() is exactly P DMA instructions, so the counted
   // waits stay exact.  Branch-free (wave-uniform selects), so the whole K loop body is one scheduling region.
   int ld_kt = kt_begin;
   int ld_chunk = kt_begin / a.T;
@@ -186,57 +145,16 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void conv_igemm_planes_kernel(
     ld_tap = wrap ? 0 : ld_tap;
     ld_chunk += wrap;
   };
-  auto emit = [&](int stage, auto qb_c, auto qe_c) {  // row blocks [qb, qe) of the prepared tile
-    constexpr int QB = decltype(qb_c)::value, QE = decltype(qe_c)::value;
+  auto emit = [&](int stage) {
     unsigned char* st = lds + stage * STAGE;
 #pragma unroll
-    for (int q = QB; q < QE; ++q)
+    for (int q = 0; q < QN; ++q)
 #pragma unroll
       for (int p = 0; p < NP; ++p)
         __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(nxt_src[q] + p * 64), (ldsbp)(st + q_dst[q] + p * q_pst[q]), 16, 0, 0);
   };
-  // L2 prefetch: the tile the DMA stream reaches PFD steps from now is touched with one 4-byte load per lane at the very addresses
-  // its DMA will use.  The first tap of every 32-channel chunk reads activation lines no block has touched yet (the producer wrote
-  // them through ANOTHER XCD's L2), and a counted vmcnt wait is only as fast as the slowest line of the tile: without the touch one
-  // step in nine waits for an HBM round trip.  The loads share vmcnt with the DMAs (in order), hence one per row block and step in
-  // every wave, so the counted waits stay exact; their destination register is never read.
-  constexpr int PFD = DD3D_PREFETCH_DISTANCE;
-  constexpr int PFN = PFD > 0 ? QN : 0;
-  int pf_kt = kt_begin, pf_chunk = kt_begin / a.T, pf_tap = kt_begin - (kt_begin / a.T) * a.T;
-  unsigned pf_sink[QN];
-#pragma unroll
-  for (int q = 0; q < QN; ++q) pf_sink[q] = 0;
-  auto pf_advance = [&]() {
-    const int adv = pf_kt + 1 < kt_end;
-    pf_kt += adv;
-    pf_tap += adv;
-    const int wrap = pf_tap == a.T;
-    pf_tap = wrap ? 0 : pf_tap;
-    pf_chunk += wrap;
-  };
-  auto prefetch = [&]() {
-    if constexpr (PFD > 0) {
-      const int dh = (pf_tap * a.kw_magic) >> 16;
-      const int dw = pf_tap - dh * a.KW;
-      const long koff_a = (long)pf_chunk * in_cstride + ((long)dh * s.W + dw) * (NP * 64);
-      const long koff_b = (long)pf_kt * (NP * 64);
-#pragma unroll
-      for (int q = 0; q < QN; ++q) {
-        const bool ok = (int)!q_isA[q] | ((int)((unsigned)(a_hi0[q] + dh) < (unsigned)s.H) & (int)((unsigned)(a_wi0[q] + dw) < (unsigned)s.W));
-        const gcbp src = ok ? q_src[q] + (q_isA[q] ? koff_a : koff_b) : g_zero + slot16;
-        // "+v": one register chain for the whole loop -- a plain output would be dead right after each definition, and the allocator
-        // could hand the register to something else while the load is still in flight
-        asm volatile("global_load_dword %0, %1, off" : "+v"(pf_sink[q]) : "v"(src) : "memory");
-      }
-      pf_advance();
-    }
-  };
-  constexpr std::integral_constant<int, 0> Q0{};
-  constexpr std::integral_constant<int, QN> QALL{};
-  // variant 2: the first QH row blocks of a tile go out after the barrier that frees their stage, the rest before the next one
-  constexpr bool SPLIT = DD3D_SCHED_VARIANT == 2 && NS >= 3 && QN >= 2;
-  constexpr int QH = SPLIT ? (QN + 1) / 2 : QN;
-  constexpr std::integral_constant<int, QH> QMID{};
+  // (An L2 touch of every tile a few steps ahead of its DMA -- one 4-byte load per lane at the DMA's addresses -- was measured slower:
+  // towers 110 -> 115 us, small convs 22 -> 31 us.  The loop is bound by vector-memory instruction throughput, not by miss latency.)
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -277,145 +195,63 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void conv_igemm_planes_kernel(
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-#if DD3D_EPI_T  // filter fragment first: the accumulator block is [channel][pixel] (conv_common.h::conv_epilogue_t)
+          // filter fragment first: the accumulator block is [channel][pixel] (conv_common.h::conv_epilogue_t)
           if constexpr (Planes<MODE>::F16)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fb[c][j][PB_[t]]), __builtin_bit_cast(f16x8, fa[c][i][PA_[t]]),
                                                                acc[i][j], 0, 0, 0);
           else
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[c][j][PB_[t]], fa[c][i][PA_[t]], acc[i][j], 0, 0, 0);
-#else
-          if constexpr (Planes<MODE>::F16)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[c][i][PA_[t]]), __builtin_bit_cast(f16x8, fb[c][j][PB_[t]]),
-                                                               acc[i][j], 0, 0, 0);
-          else
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[c][i][PA_[t]], fb[c][j][PB_[t]], acc[i][j], 0, 0, 0);
-#endif
   };
   constexpr std::integral_constant<int, 0> C0{};
   constexpr std::integral_constant<int, 1> C1{};
 
-#if DD3D_EPI_T
-  static_assert(PW == 0, "the transposed epilogue stages its vectors in the unspecialised prologue");
   EpiVec<BN, NTHR> evv;
   if (ntile <= 0) {  // an empty K slice: the split-K exchange's barriers publish the vectors
     epi_load_vectors<BN, NTHR>(a, s, n0, tid, evv);
     epi_store_vectors<BN, NTHR>(lds + EV_OFF, tid, evv);
   }
-#endif
-  if constexpr (PW > 0) {
-    if (ntile > 0) {
-      if (loader) {
-        // ---- loader waves: ring fill, then per K-tile: addresses -> [tile kt+1 landed] -> barrier -> DMA of tile kt+NS
-#pragma unroll
-        for (int d = 0; d < NS; ++d) {
-          prepare();
-          emit(d, Q0, QALL);
-        }
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 1) * P) : "memory");
-        __builtin_amdgcn_s_barrier();
-        int stage = 0;
-        for (int kt = 0; kt < ntile; ++kt) {
-          prepare();
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * P) : "memory");
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
-          emit(stage, Q0, QALL);
-          stage = stage == NS - 1 ? 0 : stage + 1;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // surplus fetches land before the block may release its LDS
-        return;
-      }
-      // ---- compute waves: fragments + MFMAs only
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      read_frags(0, C0);
-      int stage = 0;
-      constexpr int NM = TM * TN * NPROD, NDS = (TM + TN) * NP;
-      for (int kt = 0; kt < ntile; ++kt) {
-        read_frags(stage, C1);
-        mfma_chunk(C0);
-        sched_uniform<NM, NDS, 0>();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        stage = stage == NS - 1 ? 0 : stage + 1;
-        read_frags(stage, C0);
-        mfma_chunk(C1);
-        sched_uniform<NM, NDS, 0>();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else if (loader) {
-      return;
-    }
-  } else
   if (ntile > 0) {
-#if DD3D_EPI_T
     epi_load_vectors<BN, NTHR>(a, s, n0, tid, evv);  // (oldest vector-memory operations of the wave: landed by the prologue's counted wait)
-#endif
-    // prologue: fill the ring (tiles 0 .. NS-1; variant 2 leaves the second part of tile NS-1 to the first step), wait for tile 0
+    // prologue: fill the ring (tiles 0 .. NS-1), wait for tile 0
 #pragma unroll
     for (int d = 0; d < NS; ++d) {
       prepare();
-      if (SPLIT && d == NS - 1) emit(d, Q0, QMID);
-      else emit(d, Q0, QALL);
+      emit(d);
     }
-    if constexpr (PFD > 0) {  // the touch stream starts NS + PFD tiles in: tiles NS .. NS+PFD-1 go untouched (one start-up latency)
-      for (int d = 0; d < NS + PFD; ++d) pf_advance();
-    }
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SPLIT ? (NS - 2) * P + QH * NP : (NS - 1) * P) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 1) * P) : "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#if DD3D_EPI_T
     epi_store_vectors<BN, NTHR>(lds + EV_OFF, tid, evv);  // published by the first step's barrier
-#endif
     read_frags(0, C0);
-    int stage = 0;        // ring stage of tile kt
-    int fill = NS - 1;    // variant 2: stage whose tile is half issued
+    int stage = 0;  // ring stage of tile kt
     constexpr int NM = TM * TN * NPROD, NDS = (TM + TN) * NP;
     for (int kt = 0; kt < ntile; ++kt) {
-      // ---- phase A: chunk-1 fragment reads of tile kt under the chunk-0 MFMAs (variant 2: + the second part of the tile in flight),
-      // and the addresses of the next tile to fetch
-      if constexpr (SPLIT) emit(fill, QMID, QALL);
+      // ---- phase A: chunk-1 fragment reads of tile kt under the chunk-0 MFMAs, and the addresses of the next tile to fetch
       read_frags(stage, C1);
       mfma_chunk(C0);
       prepare();
-      if constexpr (DD3D_SCHED_VARIANT == 0) sched_interleave<NM, NDS, 0>();
-      else sched_uniform<NM, NDS, SPLIT ? (QN - QH) * NP : 0>();
+      sched_uniform<NM, NDS, 0>();
       __builtin_amdgcn_sched_barrier(0);
       // my pieces of tile kt+1 have landed once at most NS-2 newer tiles are in flight; my reads of this stage are done
-      // (in issue order behind tile kt+1: its step's PFN touches, then NS-2 steps of P DMAs + PFN touches)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * (P + PFN) + (SPLIT ? 0 : PFN)) : "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * P) : "memory");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // everyone: tile kt+1 landed, stage `stage` (tile kt) no longer read
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       // ---- phase B: DMA of tile kt+NS into the stage just freed and chunk-0 fragment reads of tile kt+1 under the chunk-1 MFMAs
-      if constexpr (SPLIT) {
-        emit(stage, Q0, QMID);
-        fill = stage;
-      } else {
-        emit(stage, Q0, QALL);
-      }
-      prefetch();
+      emit(stage);
       stage = stage == NS - 1 ? 0 : stage + 1;
       read_frags(stage, C0);  // (past the end: a stage holding surplus data, never used)
       mfma_chunk(C1);
-      if constexpr (DD3D_SCHED_VARIANT == 0) sched_interleave<NM, NDS, P>();
-      else sched_uniform<NM, NDS, (SPLIT ? QH * NP : P) + PFN>();
+      sched_uniform<NM, NDS, P>();
       __builtin_amdgcn_sched_barrier(0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // surplus prefetches must land before the LDS is released
-#pragma unroll
-    for (int q = 0; q < QN; ++q) asm volatile("" ::"v"(pf_sink[q]));  // the touch registers stay allocated until here
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // surplus fetches must land before the LDS is released
   }
 
   if constexpr (SK) {
     if (!splitk_exchange<TM, TN, NTHR>(a, acc, bid, tid, blockIdx.y)) return;
   }
-#if DD3D_EPI_T
-#if DD3D_EPI_LDS
   // plane stores staged through LDS (conv_epilogue_t): the rings are dead, but other waves' surplus LDS-DMAs / fragment reads of the last
   // K steps may still touch them -- every wave has waited for its own (vmcnt(0) above), one barrier makes that true for all of them
   unsigned char* scratch = nullptr;
@@ -424,12 +260,6 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void conv_igemm_planes_kernel(
     scratch = lds + wave * (NP * 2048);
   }
   conv_epilogue_t<TM, TN, MODE, WM, WN>(a, s, acc, m0, n0, wm, wn, lane, lds + EV_OFF, scratch);
-#else
-  conv_epilogue_t<TM, TN, MODE, WM, WN>(a, s, acc, m0, n0, wm, wn, lane, lds + EV_OFF, nullptr);
-#endif
-#else
-  conv_epilogue<TM, TN, MODE, WM, WN>(a, s, acc, m0, n0, wm, wn, lane);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
@@ -437,9 +267,7 @@ template <int TM, int TN, int WM, int WN, int MODE, bool ALLOW_SK = true>
 static int launch_planes_tile(const ConvKArgs& ka, hipStream_t st) {
   constexpr int NP = Planes<MODE>::NP;
   constexpr int BM = TM * 32 * WM, BN = TN * 32 * WN;
-  // loader waves (warp-specialised form) for the big 8-wave tiles, whose blocks own a CU for hundreds of K-tiles
-  constexpr int PW = (WM * WN == 8 && TM * TN >= 2) ? DD3D_PRODUCER_WAVES : 0;
-  constexpr int NTHR = 64 * (WM * WN + PW);
+  constexpr int NTHR = 64 * WM * WN;
   constexpr int STAGE = NP * (BM + BN) * 64;
   // LDS ring budgets (KiB): what a block may take decides how many blocks -- of this launch or of another stream's -- share a CU
   constexpr int BUDGET = ((WM * WN == 8 || STAGE > 32 * 1024) ? DD3D_LDS_KIB_8W : DD3D_LDS_KIB_4W) * 1024;  // (a big 4-wave tile owns its CU anyway)
@@ -449,19 +277,19 @@ static int launch_planes_tile(const ConvKArgs& ka, hipStream_t st) {
   dim3 grid(ka.ntiles * ka.nn, ka.splitk, 1);
   static unsigned long long attr_done[4];
   if (lds_opt_in_needed(attr_done)) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv_igemm_planes_kernel<TM, TN, WM, WN, NS, MODE, false, PW>), (size_t)(lds), "dynamic LDS opt-in") != DD3D_OK) return DD3D_E_LAUNCH;
+    if (lds_opt_in(reinterpret_cast<const void*>(conv_igemm_planes_kernel<TM, TN, WM, WN, NS, MODE, false>), (size_t)(lds), "dynamic LDS opt-in") != DD3D_OK) return DD3D_E_LAUNCH;
     if constexpr (ALLOW_SK)
-      if (lds_opt_in(reinterpret_cast<const void*>(conv_igemm_planes_kernel<TM, TN, WM, WN, NS, MODE, true, PW>), (size_t)(lds), "dynamic LDS opt-in") != DD3D_OK) return DD3D_E_LAUNCH;
+      if (lds_opt_in(reinterpret_cast<const void*>(conv_igemm_planes_kernel<TM, TN, WM, WN, NS, MODE, true>), (size_t)(lds), "dynamic LDS opt-in") != DD3D_OK) return DD3D_E_LAUNCH;
     lds_opt_in_done(attr_done);  // (every opt-in of this call site succeeded on this device)
   }
   if constexpr (!ALLOW_SK) DD3D_REQUIRE(ka.splitk == 1, "dd3d_conv2d_igemm_f32: this tile has no split-K form (its accumulators fill the register file)");
   if constexpr (ALLOW_SK) {
     if (ka.splitk > 1) {
-      hipLaunchKernelGGL((conv_igemm_planes_kernel<TM, TN, WM, WN, NS, MODE, true, PW>), grid, dim3(NTHR), lds, st, ka);
+      hipLaunchKernelGGL((conv_igemm_planes_kernel<TM, TN, WM, WN, NS, MODE, true>), grid, dim3(NTHR), lds, st, ka);
       return check_launch("launch_planes_tile split-K kernel");
     }
   }
-  hipLaunchKernelGGL((conv_igemm_planes_kernel<TM, TN, WM, WN, NS, MODE, false, PW>), grid, dim3(NTHR), lds, st, ka);
+  hipLaunchKernelGGL((conv_igemm_planes_kernel<TM, TN, WM, WN, NS, MODE, false>), grid, dim3(NTHR), lds, st, ka);
   return check_launch("conv_igemm_planes kernel");
 }
 

@@ -27,26 +27,6 @@ DD3D_NOTE_BUILD_FLAGS
 #ifndef DD3D_ROW_LDS_KIB_4W
 #define DD3D_ROW_LDS_KIB_4W 76
 #endif
-#ifndef DD3D_EPI_LDS
-#define DD3D_EPI_LDS 1  // 1: the transposed epilogue stages its plane stores through LDS (1 KiB of consecutive bytes per store instruction); 0: straight from the registers (A/B)
-#endif
-#ifndef DD3D_EPI_T
-#define DD3D_EPI_T 1  // 1: transposed accumulators + the 16-bytes-per-lane epilogue (conv_common.h::conv_epilogue_t); 0: round-3 form (A/B)
-#endif
-
-#ifndef DD3D_ROW_B_WAVES
-#define DD3D_ROW_B_WAVES 0  // > 0: in the 8-wave tiles only the first DD3D_ROW_B_WAVES waves (one per SIMD: the ones the MFMA arbiter favours) issue the filter stages' LDS-DMA (measured neutral: r06o)
-#endif
-#ifndef DD3D_ROW_PRIO_SLICE
-#define DD3D_ROW_PRIO_SLICE 0  // 8-wave tiles: 1: waves 4-7 run at priority 2 in the first half of a barrier interval and 0 in the second (waves 0-3 stay at 1): the
-                               // second-served wave of a SIMD goes FIRST for half its MFMAs, so that nobody runs the end of the interval alone; 2: the roles swapped
-#endif
-#ifndef DD3D_ROW_B_WAVES_HI
-#define DD3D_ROW_B_WAVES_HI 0  // 1: the LAST DD3D_ROW_B_WAVES waves issue the filter pieces (the ones the arbiter serves second: they issue while the first run their MFMAs)
-#endif
-#ifndef DD3D_ROW_B_SADDR
-#define DD3D_ROW_B_SADDR 1  // 1: filter pieces use the scalar-base form of the LDS-DMA (s[base] + a constant 32-bit lane offset: no per-piece address arithmetic, half the address registers; round 6: towers -0.8 %, one image -1.1 %, profiles/r06o_bwaves_ab.txt); 0: the builtin's 64-bit-per-lane form (A/B)
-#endif
 #ifndef DD3D_ROW_STAMP
 #define DD3D_ROW_STAMP 0  // 1: every wave of the first 512 blocks records s_memtime stamps of its phases (timing probe: dd3d_debug_row_stamps; results unchanged)
 #endif
@@ -76,32 +56,20 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
   constexpr int A_STAGE = NP * PLA, B_STAGE = NP * PLB;
   constexpr int B_BASE = NSA * A_STAGE;
   constexpr int NPA = (AROWS / 16) * NP, NPB = (BN / 16) * NP;  // 1-KiB pieces of an A stage / a B stage
-  // Filter (B) pieces may be issued by the first BW waves only (DD3D_ROW_B_WAVES): of the two waves that share a SIMD the matrix pipe serves the
-  // first-dispatched one first (measured: its 48 MFMAs of a step are out after 2370 cycles, the other's after 3590, profiles/r06n_*), so the
-  // second runs the end of every step ALONE and each of its LDS-DMA issue stalls (~60 cycles a piece) idles the pipe; the favoured wave's stalls
-  // are covered by the other's MFMAs.  Built, parity-green, and measured NEUTRAL (towers 322 vs 321 us, profiles/r06o_bwaves_ab.txt): a knob, off.
-  constexpr int BW = (NW == 8 && DD3D_ROW_B_WAVES > 0 && DD3D_ROW_B_WAVES < NW) ? DD3D_ROW_B_WAVES : NW;
-  constexpr int PA = (NPA + NW - 1) / NW, PB = (NPB + BW - 1) / BW;  // per wave (the surplus re-fetches the last piece)
+  constexpr int PA = (NPA + NW - 1) / NW, PB = (NPB + NW - 1) / NW;  // per wave (the surplus re-fetches the last piece)
   constexpr int ZERO_OFF = B_BASE + NSB * B_STAGE;  // 16 zero bytes invalid taps read (64 reserved)
   constexpr int EV_OFF = ZERO_OFF + 64;              // [scale | bias | lo][BN] floats of the epilogue (conv_epilogue_t)
-  static_assert(NSB >= 2 && NSB <= 6 && NSA >= 2 && NSA <= 4 && EV_OFF + 12 * BN <= 160 * 1024, "LDS rings");
+  static_assert(NSA == 2 && (NSB == 2 || NSB == 3) && EV_OFF + 12 * BN <= 160 * 1024, "LDS rings");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   unsigned char* lds = reinterpret_cast<unsigned char*>(smem);
   typedef unsigned char __attribute__((address_space(3))) * ldsbp;
-#if DD3D_ROW_B_SADDR
   const unsigned lds_base32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(ldsbp)lds);  // LDS byte address of the rings (M0 of the scalar-base LDS-DMA)
-#endif
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN;
   const int wn = wave - wm * WN;
-#if DD3D_ROW_PRIO_SLICE
-  const bool prio_wave = NW == 8 && (DD3D_ROW_PRIO_SLICE == 1 ? wave >= 4 : wave < 4);  // the waves that alternate between priority 2 and 0
-  if (NW == 8 && !prio_wave) __builtin_amdgcn_s_setprio(1);
-#endif
-  const bool bwave = BW == NW || (DD3D_ROW_B_WAVES_HI ? wave >= NW - BW : wave < BW);  // (wave-uniform) this wave issues filter pieces
 #if DD3D_ROW_STAMP
   unsigned long long st_t[8] = {stamp_now(), 0, 0, 0, 0, 0, 0, 0};
   unsigned long long st_last = 0;
@@ -147,28 +115,17 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
     a_dst[q] = pl * PLA + rb * 1024;
     a_pix[q] = m0 - 1 + rb * 16 + (lane >> 2);
   }
-#if DD3D_ROW_B_SADDR
   unsigned b_src[PB];  // byte offset of this lane's filter row from the filter base: K-tile 0, plane and k-slot included
-#else
-  gcbp b_src[PB];  // this lane's filter row, K-tile 0, plane and k-slot included
-#endif
   int b_dst[PB];
 #pragma unroll
   for (int q = 0; q < PB; ++q) {
-    const int piece = min(q * BW + (BW == NW ? wave : wave % BW), NPB - 1);
+    const int piece = min(q * NW + wave, NPB - 1);
     const int rb = piece / NP, pl = piece - rb * NP;
-#if DD3D_EPI_T  // LDS row R of the B stage holds filter row chan_of_row(R) of its 32-row block (conv_common.h::conv_epilogue_t)
+    // LDS row R of the B stage holds filter row chan_of_row(R) of its 32-row block (conv_common.h::conv_epilogue_t)
     const int brow = rb * 16 + (lane >> 2);
     const int n = min(n0 + (brow & ~31) + chan_of_row(brow & 31), a.Npad - 1);  // rows past Npad feed columns >= N, which are never stored
-#else
-    const int n = min(n0 + rb * 16 + (lane >> 2), a.Npad - 1);  // rows past Npad feed columns >= N, which are never stored
-#endif
     b_dst[q] = B_BASE + pl * PLB + rb * 1024;
-#if DD3D_ROW_B_SADDR
     b_src[q] = (unsigned)((long)n * nk * (NP * 64) + pl * 64 + slot16);  // (launch_conv_planes_row checks that the filter stays below 4 GiB)
-#else
-    b_src[q] = g_w + (long)n * nk * (NP * 64) + pl * 64 + slot16;
-#endif
   }
 
   // ---- streams: A walks the groups (chunk, dh), B walks the K-tiles; past the end both re-fetch their last element (exact DMA counts)
@@ -193,7 +150,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
   };
   auto emit_b = [&](int stage) {  // K-tile ld_kt, then advance
     const long koff = (long)ld_kt * (NP * 64);
-#if DD3D_ROW_B_SADDR
+    // Filter pieces use the scalar-base form of the LDS-DMA (s[base] + a constant 32-bit lane offset: no per-piece address arithmetic, half the
+    // address registers; against the builtin's 64-bit-per-lane form round 6 measured towers -0.8 %, one image -1.1 %, profiles/r06o_bwaves_ab.txt).
     // global_load_lds_dwordx4 vOFFSET, s[BASE:BASE+1]: address = base + zext(lane offset); the LDS destination of the wave instruction = M0 + 16 lane.
     // (The builtin only emits the 64-bit-per-lane form.  The compiler does not see these loads: its own waits only get more conservative --
     // vector-memory loads return in order -- and the K loop's waits are explicit.)
@@ -211,11 +169,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
     for (int q = 0; q < PB; ++q)
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds0 + (unsigned)b_dst[q]), "v"(b_src[q]), "s"(kbase) : "memory", "m0");
 #pragma clang diagnostic pop
-#else
-#pragma unroll
-    for (int q = 0; q < PB; ++q)
-      __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(b_src[q] + koff), (ldsbp)(lds + stage * B_STAGE + b_dst[q]), 16, 0, 0);
-#endif
     ld_kt += (ld_kt + 1 < kt_end);
   };
 
@@ -300,57 +253,43 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-#if DD3D_EPI_T  // filter fragment first: the accumulator block is [channel][pixel] (conv_common.h::conv_epilogue_t)
+          // filter fragment first: the accumulator block is [channel][pixel] (conv_common.h::conv_epilogue_t)
           if constexpr (Planes<MODE>::F16)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fb[c][j][PB_[t]]), __builtin_bit_cast(f16x8, fa[c][i][PA_[t]]),
                                                                acc[i][j], 0, 0, 0);
           else
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[c][j][PB_[t]], fa[c][i][PA_[t]], acc[i][j], 0, 0, 0);
-#else
-          if constexpr (Planes<MODE>::F16)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[c][i][PA_[t]]), __builtin_bit_cast(f16x8, fb[c][j][PB_[t]]),
-                                                               acc[i][j], 0, 0, 0);
-          else
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[c][i][PA_[t]], fb[c][j][PB_[t]], acc[i][j], 0, 0, 0);
-#endif
   };
   constexpr std::integral_constant<int, 0> C0{};
   constexpr std::integral_constant<int, 1> C1{};
 
   if (tid < 4) reinterpret_cast<int*>(lds + ZERO_OFF)[tid] = 0;  // (visible to every wave after the prologue's barrier)
-#if DD3D_EPI_T
   EpiVec<BN, NTHR> evv;
   epi_load_vectors<BN, NTHR>(a, s, n0, tid, evv);  // (oldest vector-memory operations of the wave: landed by the prologue's counted wait)
   if (ngroup <= 0) epi_store_vectors<BN, NTHR>(lds + EV_OFF, tid, evv);  // (an empty K slice: the split-K exchange's barriers publish them)
-#endif
   if (ngroup > 0) {
     // prologue.  The loop's counted waits assume the STEADY-STATE issue order -- step t issues B(t + NSB) and, when its dw == 2, the A group
-    // NSA groups ahead behind it -- so the prologue issues in the order the (virtual) steps t = -NSB .. -1 would have: A group NSA - k sits
-    // behind the B of virtual step -(3 k - 2), i.e. behind B(NSB + 2 - 3 k); the groups whose virtual step lies before the window come first.
-    //   NSB <= 3, NSA = 2 (the product rings):  A(0) | B(0 .. NSB-1) | A(1)
-    //   NSB = 5, NSA = 3:                       A(0) | B(0) B(1) | A(1) | B(2) B(3) B(4) | A(2)    (virtual steps -4 and -1 have dw == 2)
-    // Then wait for A(0) and B(0): everything issued after the later of the two may stay in flight.
-    constexpr int UPFRONT = (1 <= NSA && 1 > NSB) + (2 <= NSA && 4 > NSB) + (3 <= NSA && 7 > NSB) + (4 <= NSA && 10 > NSB);  // k: 3 k - 2 > NSB
+    // two groups ahead behind it -- so the prologue issues in the order the (virtual) steps t = -NSB .. -1 would have:
+    //   A(0) | B(0 .. NSB-1) | A(1)          (virtual step -1 has dw == 2; A(0)'s virtual step lies before the window)
+    // Then wait for A(0) and B(0): everything issued after B(0) -- the other B tiles and A(1) -- may stay in flight.
+    // (Spelt with the one-trip loop and the running stage index of the any-ring-depth form it replaces.  Straight-line -- A(0); the B loop;
+    // A(1) -- is the same program, but the compiler then schedules and allocates the whole kernel differently; that spelling goes in with
+    // the next change that is measured on the GPU anyway.)
     int next_a = 0;
 #pragma unroll
-    for (int u = 0; u < UPFRONT; ++u) {
+    for (int u = 0; u < 1; ++u) {
       prepare_a();
       emit_a(next_a++);
     }
 #pragma unroll
     for (int d = 0; d < NSB; ++d) {
-      if (bwave) emit_b(d);
-      const int k3 = NSB + 2 - d;  // = 3 k of the A group that follows this B, if any
-      if (k3 % 3 == 0 && k3 / 3 >= 1 && k3 / 3 <= NSA) {
+      emit_b(d);
+      if (d == NSB - 1) {
         prepare_a();
         emit_a(next_a++);
       }
     }
-    constexpr int DA0 = NSB + 2 - 3 * NSA;  // (UPFRONT == 0) A(0) follows B(DA0)
-    constexpr int PRO_WAIT = UPFRONT > 0 ? (NSB - 1) * PB + (NSA - UPFRONT) * PA : (NSB - 1 - DA0) * PB + (NSA - 1) * PA;
-    constexpr int PRO_WAIT_NOB = UPFRONT > 0 ? (NSA - UPFRONT) * PA : (NSA - 1) * PA;  // a wave without filter pieces: only its A groups count
-    if (bwave) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PRO_WAIT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PRO_WAIT_NOB) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSB - 1) * PB + PA) : "memory");
 #if DD3D_ROW_STAMP
     st_t[1] = stamp_now();
 #endif
@@ -359,25 +298,15 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
 #if DD3D_ROW_STAMP
     st_t[2] = st_last = stamp_now();
 #endif
-#if DD3D_EPI_T
     epi_store_vectors<BN, NTHR>(lds + EV_OFF, tid, evv);  // published by the first step's barrier
-#endif
     read_frags(0, 0, 0, (g_begin % 3) * 3, C0);
     int sb = 0;
     // One step = one K-tile (filter row dh, column dw).  DMA issue order after the prologue: step s issues B(s + NSB) and, when dw == 2
-    // (the group's A stage has just been read for the last time), A(group + NSA) behind it.  "B(s+1) has landed" at step s therefore
+    // (the group's A stage has just been read for the last time), A(group + 2) behind it.  "B(s+1) has landed" at step s therefore
     // means: at most the B tiles s+2 .. s+NSB-1 and the A groups issued in steps s+1-NSB .. s-1 are still in flight (in the first steps
-    // the prologue's extra A groups sit behind B(1) as well: the counted wait then also waits for them -- conservative, never wrong).
-    // NSA A stages = the A stream runs NSA - 1 groups (3 (NSA - 1) K steps) ahead: the activations of a block are read ONCE, so every
-    // A group is an HBM / MALL round trip, and the short steps of the small tiles (a few hundred cycles) do not cover one with NSA = 2.
+    // the prologue's A(1) sits behind B(1) as well: the counted wait then also waits for it -- conservative, never wrong).
     auto step = [&](int sa, int dh, auto dw_c) {
       constexpr int dw = decltype(dw_c)::value;
-#if DD3D_ROW_PRIO_SLICE
-      if constexpr (NW == 8) {  // second half of the barrier interval
-        if (prio_wave) __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#endif
       const int tap = dh * 3 + dw;
       // ---- phase A: chunk-1 fragments under the chunk-0 MFMAs; addresses of the next A group (used after the barrier when dw == 2)
       read_frags(sa, sb, dw, tap, C1);
@@ -385,22 +314,13 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
       if constexpr (dw == 2) prepare_a();
       sched_barrier_phase<TM * TN * NPROD, (TM + TN) * NP, 0>();
       // "B(s+1) has landed": B(s+1) was issued in step s+1-NSB; behind it sit the B tiles s+2 .. s+NSB-1 and the A groups issued in the steps
-      // s+1-NSB .. s-1, i.e. one per step j = 1 .. NSB-1 back whose dw was 2.  When dw == 2 the next A group is read right after this barrier:
-      // it was issued 3 (NSA - 1) steps ago behind that step's B, so at most the 3 (NSA - 1) - 1 B tiles and NSA - 2 A groups issued since may
-      // stay in flight (a no-op tightening for the product rings).
-      constexpr int a_in_flight = ((dw + 2) % 3 == 2 && NSB > 1) + ((dw + 1) % 3 == 2 && NSB > 2) + ((dw + 0) % 3 == 2 && NSB > 3) +
-                                  ((dw + 2) % 3 == 2 && NSB > 4) + ((dw + 1) % 3 == 2 && NSB > 5);  // j = 1 .. 5: (dw - j) mod 3 == 2
-      constexpr int steady = (NSB - 2) * PB + a_in_flight * PA;
-      constexpr int a_cap = (3 * (NSA - 1) - 1) * PB + (NSA - 2) * PA;
-      constexpr int wait_n = (dw == 2 && steady > a_cap) ? a_cap : steady;
-      // (a wave without filter pieces, DD3D_ROW_B_WAVES: the same counts with PB = 0)
-      constexpr int steady_nob = a_in_flight * PA, a_cap_nob = (NSA - 2) * PA;
-      constexpr int wait_nob = (dw == 2 && steady_nob > a_cap_nob) ? a_cap_nob : steady_nob;
+      // s+1-NSB .. s-1, i.e. one when one of the NSB - 1 steps before this one had dw == 2.  (When dw == 2 the next A group is read right after
+      // this barrier: it was issued three steps ago behind that step's B, and fewer than the two B tiles issued since stay in flight.)
+      constexpr int a_in_flight = NSB == 3 ? dw != 2 : dw == 0;
 #if DD3D_ROW_STAMP
       const unsigned long long st_a = stamp_now();  // (its lgkmcnt(0) = the fragment reads of this phase have landed)
 #endif
-      if (BW == NW || bwave) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_n) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_nob) : "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSB - 2) * PB + a_in_flight * PA) : "memory");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #if DD3D_ROW_STAMP
       const unsigned long long st_b = stamp_now();
@@ -415,20 +335,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
       }
 #endif
       __builtin_amdgcn_sched_barrier(0);
-#if DD3D_ROW_PRIO_SLICE
-      if constexpr (NW == 8) {  // first half of the barrier interval
-        if (prio_wave) __builtin_amdgcn_s_setprio(2);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#endif
       // ---- phase B: refill the freed stages; chunk-0 fragments of the next K-tile under the chunk-1 MFMAs
-#if DD3D_ROW_STAMP > 1  // (2: slot [6] = the filter pieces' issue instead of the vmcnt wait)
-      const unsigned long long st_d = stamp_now();
-#endif
-      if (BW == NW || bwave) emit_b(sb);
-#if DD3D_ROW_STAMP > 1
-      st_t[6] += stamp_now() - st_d - (st_b - st_a);
-#endif
+      emit_b(sb);
       if constexpr (dw == 2) emit_a(sa);
       sb = sb == NSB - 1 ? 0 : sb + 1;
       constexpr int ndw = dw == 2 ? 0 : dw + 1;
@@ -436,7 +344,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
       const int ndh = dw == 2 ? (dh == 2 ? 0 : dh + 1) : dh;
       read_frags(nsa, sb, ndw, ndh * 3 + ndw, C0);  // (past the end: surplus data, never used)
       mfma_chunk(C1);
-      sched_barrier_phase<TM * TN * NPROD, (TM + TN) * NP, (BW == NW && !DD3D_ROW_B_SADDR ? PB : 0) + (dw == 2 ? PA : 0)>();
+      sched_barrier_phase<TM * TN * NPROD, (TM + TN) * NP, dw == 2 ? PA : 0>();  // (the filter pieces are inline assembly: not VMEM instructions the scheduler could place)
     };
     constexpr std::integral_constant<int, 0> D0{};
     constexpr std::integral_constant<int, 1> D1{};
@@ -459,8 +367,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
   if constexpr (SK) {
     if (!splitk_exchange<TM, TN, NTHR>(a, acc, bid, tid, kslice)) return;
   }
-#if DD3D_EPI_T
-#if DD3D_EPI_LDS
   // plane stores staged through LDS (conv_epilogue_t): the rings are dead, but other waves' surplus LDS-DMAs / fragment reads of the last
   // K steps may still touch them -- every wave has waited for its own (vmcnt(0) above), one barrier makes that true for all of them
   unsigned char* scratch = nullptr;
@@ -469,12 +375,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
     scratch = lds + wave * (NP * 2048);
   }
   conv_epilogue_t<TM, TN, MODE, WM, WN>(a, s, acc, m0, n0, wm, wn, lane, lds + EV_OFF, scratch);
-#else
-  conv_epilogue_t<TM, TN, MODE, WM, WN>(a, s, acc, m0, n0, wm, wn, lane, lds + EV_OFF, nullptr);
-#endif
-#else
-  conv_epilogue<TM, TN, MODE, WM, WN>(a, s, acc, m0, n0, wm, wn, lane);
-#endif
 #if DD3D_ROW_STAMP
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the stores acknowledged: what the next launch waits for)
   st_t[4] = stamp_now();
@@ -487,9 +387,10 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_planes_row_kernel(con
 
 // ------------------------------------------------------------------------------------------------------------------ host
 // Ring depths of a tile (also computed by dd3d_amd/engine/tiling.py::kernel_signature for the bench's bookkeeping):
+//   NSA  A stages: 2
 //   NSB  B stages: 3 when two A stages + three B stages fit the block's LDS budget, else 2
-//   NSA  A stages: as many (<= 4) as fit -- a block that fits twice into a CU with NSA = 2 (<= 80 KiB) keeps fitting twice, a block that
-//        owns its CU anyway may grow to the whole budget
+// Deeper rings (up to 4 A / 6 B stages, as far as the budget allowed) were built and measured in round 5 and not kept:
+// profiles/r04i_a_ring_depth_ab.txt, r05g_b_ring_depth_ab.txt, r05i_ring_depth_ab.txt; DESIGN.md section 4, round 5.
 template <int TM, int TN, int WM, int WN, int MODE>
 struct RowRings {
   static constexpr int NP = Planes<MODE>::NP;
@@ -497,30 +398,10 @@ struct RowRings {
   static constexpr int AST = NP * (BM + 16) * 64, BST = NP * BN * 64;
   // (a 4-wave block whose two A stages alone exceed half a CU's LDS owns its CU anyway: it takes the 8-wave budget)
   static constexpr int BUDGET = ((WM * WN == 8 || 2 * AST > 64 * 1024) ? DD3D_ROW_LDS_KIB_8W : DD3D_ROW_LDS_KIB_4W) * 1024;
-  // The product rings: two A stages; three B stages when 2 A + 3 B fit the budget, else two.  -DDD3D_ROW_NSA_MAX=3..4 / -DDD3D_ROW_NSB_MAX=4..6 let
-  // the rings grow as far as LIMIT allows -- a block that fits twice into a CU with the product rings (<= 80 KiB) keeps fitting twice, a block
-  // that owns its CU anyway may take the whole budget -- A first, then B.  Measured (profiles/r04i_a_ring_depth_ab.txt, r05g_b_ring_depth_ab.txt,
-  // r05i_ring_depth_ab.txt): see DESIGN.md section 4, round 5; the product keeps 2 + 3.
-  static constexpr int NSB0 = (2 * AST + 3 * BST <= BUDGET) ? 3 : 2;
+  static constexpr int NSA = 2;
+  static constexpr int NSB = (2 * AST + 3 * BST <= BUDGET) ? 3 : 2;
   static constexpr int EXTRA = 64 + 12 * BN;  // the zero bytes invalid taps read + the epilogue vectors
-  static constexpr int TOTAL0 = 2 * AST + NSB0 * BST + EXTRA;
-  static constexpr int LIMIT = TOTAL0 <= 80 * 1024 ? 80 * 1024 : (BUDGET > TOTAL0 ? BUDGET : TOTAL0);
-#ifdef DD3D_ROW_NSA_MAX
-  static constexpr int NSA_MAX = DD3D_ROW_NSA_MAX;
-#else
-  static constexpr int NSA_MAX = 2;
-#endif
-#ifdef DD3D_ROW_NSB_MAX
-  static constexpr int NSB_MAX = DD3D_ROW_NSB_MAX;
-#else
-  static constexpr int NSB_MAX = 3;
-#endif
-  static constexpr bool fits(int nsa, int nsb) { return nsa * AST + nsb * BST + EXTRA <= LIMIT; }
-  static constexpr int pick_nsa(int n) { return (n > 2 && !fits(n, NSB0)) ? pick_nsa(n - 1) : n; }
-  static constexpr int NSA = pick_nsa(NSA_MAX < 2 ? 2 : (NSA_MAX > 4 ? 4 : NSA_MAX));
-  static constexpr int pick_nsb(int n) { return (n > NSB0 && !fits(NSA, n)) ? pick_nsb(n - 1) : n; }
-  static constexpr int NSB = pick_nsb(NSB_MAX < NSB0 ? NSB0 : (NSB_MAX > 6 ? 6 : NSB_MAX));
-  static constexpr int total(int nsa) { return nsa * AST + NSB * BST + EXTRA; }
+  static constexpr int TOTAL = NSA * AST + NSB * BST + EXTRA;
 };
 
 template <int TM, int TN, int WM, int WN, int MODE, bool ALLOW_SK = true>
@@ -528,8 +409,8 @@ static int launch_row_tile(const ConvKArgs& ka, hipStream_t st) {
   typedef RowRings<TM, TN, WM, WN, MODE> R;
   constexpr int NTHR = 64 * WM * WN;
   constexpr int NSB = R::NSB, NSA = R::NSA;
-  static_assert(R::total(NSA) <= 160 * 1024, "tile does not fit the LDS");
-  const size_t lds = (size_t)R::total(NSA);
+  static_assert(R::TOTAL <= 160 * 1024, "tile does not fit the LDS");
+  const size_t lds = (size_t)R::TOTAL;
   dim3 grid(ka.ntiles * ka.nn, ka.splitk, 1);
   static unsigned long long attr_done[4];
   if (lds_opt_in_needed(attr_done)) {
@@ -621,10 +502,8 @@ bool conv_planes_row_applicable(const ConvKArgs& ka) {
 }
 
 int launch_conv_planes_row(const ConvKArgs& ka, int math_mode, int tile_cfg, hipStream_t st) {
-#if DD3D_ROW_B_SADDR
   // filter rows are addressed as base + a 32-bit byte offset per lane (at most 3 planes of Kpad halves per filter)
   DD3D_REQUIRE((long)ka.Npad * ka.Kpad * 6 < (1l << 32), "dd3d_conv2d_igemm_f32: filter of %d x %d beyond the 4 GiB the row kernel addresses", ka.Npad, ka.Kpad);
-#endif
   switch (math_mode) {
     case DD3D_MATH_BF16X3: return launch_row_mode<DD3D_MATH_BF16X3>(ka, tile_cfg, st);
     case DD3D_MATH_BF16X2: return launch_row_mode<DD3D_MATH_BF16X2>(ka, tile_cfg, st);

@@ -89,8 +89,8 @@ def kernel_signature(op):
 
 
 def row_rings_default(np_, bm, bn, nwaves):
-    """(NSB, NSA) of csrc/conv_planes_row.hip::RowRings for the product build (no -DDD3D_ROW_* knob); a CPU test compares it with
-    dd3d_conv_row_rings for every tile and mode."""
+    """(NSB, NSA) of csrc/conv_planes_row.hip::RowRings with the product build's LDS budgets (DD3D_ROW_LDS_KIB_4W / _8W at their defaults); a CPU
+    test compares it with dd3d_conv_row_rings for every tile and mode."""
     ast, bst = np_ * (bm + 16) * 64, np_ * bn * 64
     budget = (152 if (nwaves == 8 or 2 * ast > 65536) else 76) * 1024
     nsb = 3 if 2 * ast + 3 * bst <= budget else 2

@@ -209,7 +209,16 @@ def test_product_sources_hold_no_wrong_result_variants():
             used |= set(re.findall(r"#\s*(?:ifdef|ifndef|if)\s+(?:defined\()?(DD3D_[A-Z0-9_]+)", t))
             assert f.endswith(".h") or "DD3D_NOTE_BUILD_FLAGS" in t, f
     assert used <= listed, used - listed
-    assert os.path.exists(os.path.join(ROOT, "tests", "tools", "variants", "r04_timing_ablations.patch"))
+    # the ablation patch still applies to these sources (tests/tools/build_variant.sh --ablations applies it to a copy, the same way)
+    import shutil
+    import subprocess
+    import tempfile
+    patch = os.path.join(ROOT, "tests", "tools", "variants", "r04_timing_ablations.patch")
+    assert os.path.exists(patch)
+    with tempfile.TemporaryDirectory() as tmp:
+        shutil.copytree(csrc, os.path.join(tmp, "dd3d_amd", "csrc"))
+        r = subprocess.run(["patch", "--dry-run", "-p1", "-i", patch], cwd=tmp, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout
 
 
 def test_config_surface():
