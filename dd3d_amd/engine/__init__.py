@@ -7,6 +7,7 @@
   backbones  DLA / VoVNet-V2 / FPN lowering (mixin)
   forward    ForwardPlan (trunk, heads, select / decode / NMS, the exchange record) and DenseDepthPlan
   losses     LossPlan (trunk, heads, target assignment, loss terms) and assign_targets (DD3D.prepare_targets)
+  dense_depth_loss  DenseDepthLossPlan (DenseDepthPlan's trunk and head, then the fused per-level depth loss) and its GT staging
 
 Everything is re-exported here: `from dd3d_amd.engine import ForwardPlan, ConvOp, choose_tiling, ...` keeps working.
 """
@@ -17,4 +18,5 @@ from dd3d_amd.engine.ops import CallOp, ConvOp, FusedStemOp, OpList, SmallcConvO
 from dd3d_amd.engine.plan import HalfRangeOverflow, HalfRangeUnderflow, PlanBase, relax_arithmetic  # noqa: F401
 from dd3d_amd.engine.backbones import BackboneLowering  # noqa: F401
 from dd3d_amd.engine.forward import DenseDepthPlan, ForwardPlan  # noqa: F401
+from dd3d_amd.engine.dense_depth_loss import DenseDepthLossPlan, dense_depth_loss_config, stage_depth_canvas  # noqa: F401
 from dd3d_amd.engine.losses import LossPlan, assign_targets  # noqa: F401

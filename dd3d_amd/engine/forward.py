@@ -534,7 +534,29 @@ class DenseDepthPlan(ForwardPlan):
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
         self.adopt_weight_store(model)
         self._trunk(model, B, Hp, Wp)
-        dev, feats, head = self.device, self.features, model.fcos3d_head
+        self._dense_depth_head(model)
+        dev, feats = self.device, self.features
+        # upsample + focal scaling (tensor2d.py:28-47, dense_depth.py:140-151)
+        self.depth_maps = []
+        half = int(model.feature_locations_offset == "half")
+        for l, f in enumerate(feats):
+            stride = self.strides[l]
+            assert f.H * stride == Hp and f.W * stride == Wp, "pyramid level does not tile the padded input"
+            o = torch.zeros((B, Hp, Wp), dtype=torch.float32, device=dev)
+            self.depth_maps.append(o)
+            factor = float(model.scale_depth_by_focal_lengths_factor) if model.scale_depth_by_focal_lengths else 0.0
+
+            def _up(lib, st, src=self.dd_raw[l], o=o, stride=stride, factor=factor, f=f):
+                hip.check(lib.dd3d_aligned_bilinear_scale(src.t.data_ptr(), o.data_ptr(), self.inv_K.data_ptr(), B, f.H, f.W, 4, stride, half,
+                                                          factor, st), "aligned_bilinear")
+
+            self.ops.append(CallOp(_up, f"dd_upsample.{l}", dict(kind="aligned_bilinear_scale", src=self.dd_raw[l], out=o, factor=stride,
+                                                                   offset_half=half, focal_factor=factor)))
+
+    def _dense_depth_head(self, model):
+        """The box3d tower and the per-level predictors on the trunk's features (shared with DenseDepthLossPlan): `dd_raw`, the raw
+        1-channel maps (NHWC f32, pitch 4) the up-sampling reads."""
+        feats, head = self.features, model.fcos3d_head
         L, Cf = len(feats), feats[0].C
         ping = [self.buf(f"ddA.{l}", f.B, f.H, f.W, Cf, kind="planes") for l, f in enumerate(feats)]
         pong = [self.buf(f"ddB.{l}", f.B, f.H, f.W, Cf, kind="planes") for l, f in enumerate(feats)]
@@ -561,21 +583,3 @@ class DenseDepthPlan(ForwardPlan):
             self.dd_raw.append(out)
             segs.append({"in": cur[l], "out": out.view(0, 4), "w": w, "scale": self._vec(sc), "bias": self._vec(b * sc + off), "n_limit": 1})
         self.ops.append(ConvOp(self, meta, 1, 1, segs, relu=False, name="dd_predictors"))
-        # upsample + focal scaling (tensor2d.py:28-47, dense_depth.py:140-151)
-        self.depth_maps = []
-        half = int(model.feature_locations_offset == "half")
-        for l, f in enumerate(feats):
-            stride = self.strides[l]
-            assert f.H * stride == Hp and f.W * stride == Wp, "pyramid level does not tile the padded input"
-            o = torch.zeros((B, Hp, Wp), dtype=torch.float32, device=dev)
-            self.depth_maps.append(o)
-            factor = float(model.scale_depth_by_focal_lengths_factor) if model.scale_depth_by_focal_lengths else 0.0
-
-            def _up(lib, st, src=self.dd_raw[l], o=o, stride=stride, factor=factor, f=f):
-                hip.check(lib.dd3d_aligned_bilinear_scale(src.t.data_ptr(), o.data_ptr(), self.inv_K.data_ptr(), B, f.H, f.W, 4, stride, half,
-                                                          factor, st), "aligned_bilinear")
-
-            self.ops.append(CallOp(_up, f"dd_upsample.{l}", dict(kind="aligned_bilinear_scale", src=self.dd_raw[l], out=o, factor=stride,
-                                                                   offset_half=half, focal_factor=factor)))
-
-

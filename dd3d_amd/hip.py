@@ -170,12 +170,34 @@ class LossArgs(C.Structure):
     ]
 
 
+DDL_ROW, DDL_MAX_BLOCKS = 12, 1024
+DDL_QUADS_PER_BLOCK = 256  # dd3d_dense_depth_loss: a block of 256 threads reads 256 four-pixel groups per sweep
+
+
+def dense_depth_loss_blocks(B, Hp, Wp):
+    """Blocks (= partial rows) of one dd3d_dense_depth_loss launch on a B x Hp x Wp canvas."""
+    quads = B * Hp * (Wp // 4)
+    return min((quads + DDL_QUADS_PER_BLOCK - 1) // DDL_QUADS_PER_BLOCK, DDL_MAX_BLOCKS)
+
+
+class DenseDepthLossArgs(C.Structure):
+    """`dd3d_dense_depth_loss_args`."""
+    _fields_ = [
+        ("raw", C.c_void_p * MAX_LEVELS), ("gt", C.c_void_p), ("inv_K", C.c_void_p), ("partials", C.c_void_p), ("out", C.c_void_p),
+        ("count", C.c_void_p), ("h", C.c_int32 * MAX_LEVELS), ("w", C.c_int32 * MAX_LEVELS), ("stride", C.c_int32 * MAX_LEVELS),
+        ("divisor", C.c_float * MAX_LEVELS), ("num_levels", C.c_int32), ("B", C.c_int32), ("Hp", C.c_int32), ("Wp", C.c_int32),
+        ("pitch", C.c_int32), ("offset_half", C.c_int32), ("n_partials", C.c_int32), ("focal_factor", C.c_float), ("min_depth", C.c_float),
+        ("max_depth", C.c_float), ("beta", C.c_float), ("loss_weight", C.c_float)
+    ]
+
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
     "dd3d_invert_intrinsics", "dd3d_nms_finalize", "dd3d_bev_nms_aggregate", "dd3d_conv2d_smallc_supported", "dd3d_conv2d_smallc_bf16x3", "dd3d_rotate_iou_eval", "dd3d_d3_box_overlap", "dd3d_image_box_overlap", "dd3d_aligned_bilinear_scale", "dd3d_resize_bilinear_u8",
     "dd3d_format_boxes3d", "dd3d_math_planes", "dd3d_split_planes", "dd3d_maxpool2x2_planes", "dd3d_maxpool2x2_planes_in", "dd3d_upsample2x_add_planes", "dd3d_ese_fused", "dd3d_stem_fused_f16x2", "dd3d_fold_range_flags", "dd3d_pack_readback",
-    "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match", "dd3d_loss_assign", "dd3d_loss_terms", "dd3d_loss_layout"
+    "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match", "dd3d_loss_assign", "dd3d_loss_terms", "dd3d_loss_layout",
+    "dd3d_dense_depth_loss", "dd3d_dense_depth_loss_layout"
 ]
 
 
@@ -246,6 +268,8 @@ def lib():
     L.dd3d_loss_assign.argtypes = [C.POINTER(LossArgs), C.c_void_p]
     L.dd3d_loss_terms.argtypes = [C.POINTER(LossArgs), C.c_void_p]
     L.dd3d_loss_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_dense_depth_loss.argtypes = [C.POINTER(DenseDepthLossArgs), C.c_void_p]
+    L.dd3d_dense_depth_loss_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

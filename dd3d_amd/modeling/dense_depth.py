@@ -4,7 +4,8 @@ bilinear upsampling of every level to the input resolution and the focal-length 
 
 The reference's ``forward`` only defines the training branch (it ends in ``raise NotImplementedError()`` in eval mode,
 dense_depth.py:162-163); everything it computes before the losses is inference math, exposed here as
-``predict_dense_depth(batched_inputs)``; ``forward`` keeps the reference's eval-mode behaviour.
+``predict_dense_depth(batched_inputs)``; ``forward`` keeps the reference's eval-mode behaviour.  What the training branch adds, the
+per-level loss dict (dense_depth.py:165-171), is ``compute_losses(batched_inputs)``: values only, no gradients.
 """
 import torch
 from torch import nn
@@ -89,20 +90,23 @@ class DD3DDenseDepth(nn.Module):
         self.invalidate_plans()
         return r
 
-    def get_plan(self, B, Hp, Wp):
-        from dd3d_amd.engine import DenseDepthPlan
-        key = (B, Hp, Wp, self.math)
+    def _cached_plan(self, key, build):
+        """The plan under `key` of the bounded cache (most recently used last; bounded like DD3D.get_plan), built and captured on a miss."""
         plan = self._plans.pop(key, None)
         if plan is None:
-            plan = DenseDepthPlan(self, B, Hp, Wp)
+            plan = build()
             if self.use_graph:
                 plan.capture()
-        self._plans[key] = plan  # most recently used last; bounded like DD3D.get_plan
+        self._plans[key] = plan
         while len(self._plans) > 8:
             if torch.cuda.is_available():
                 torch.cuda.synchronize()
             self._plans.pop(next(iter(self._plans)))
         return plan
+
+    def get_plan(self, B, Hp, Wp):
+        from dd3d_amd.engine import DenseDepthPlan
+        return self._cached_plan((B, Hp, Wp, self.math), lambda: DenseDepthPlan(self, B, Hp, Wp))
 
     @torch.no_grad()
     def predict_dense_depth(self, batched_inputs):
@@ -118,7 +122,9 @@ class DD3DDenseDepth(nn.Module):
                 if not relax_arithmetic(self, e):  # (plane scale 16 -> 4 -> 1, then bf16x3; an explicitly chosen arithmetic raises)
                     raise
 
-    def _predict_dense_depth(self, batched_inputs):
+    def _stage(self, batched_inputs, get_plan):
+        """Images, sizes and intrinsics of a batch into the plan `get_plan(B, Hp, Wp)` builds for its padded canvas (ImageList.from_tensors'
+        geometry).  Returns (plan, image sizes)."""
         images = [x["image"] for x in batched_inputs]
         div = self.backbone.size_divisibility
         H = max(int(im.shape[-2]) for im in images)
@@ -126,11 +132,12 @@ class DD3DDenseDepth(nn.Module):
         if div > 1:
             H, W = (H + div - 1) // div * div, (W + div - 1) // div * div
         B = len(images)
-        plan = self.get_plan(B, H, W)
+        plan = get_plan(B, H, W)
         for i, im in enumerate(images):
             assert im.dtype == torch.uint8 and im.shape[0] == 3
             plan.in_u8[i, :, :im.shape[1], :im.shape[2]].copy_(im, non_blocking=True)
-        plan.in_sizes.copy_(torch.tensor([[int(im.shape[-2]), int(im.shape[-1])] for im in images], dtype=torch.int32), non_blocking=True)
+        sizes = [[int(im.shape[-2]), int(im.shape[-1])] for im in images]
+        plan.in_sizes.copy_(torch.tensor(sizes, dtype=torch.int32), non_blocking=True)
         if self.scale_depth_by_focal_lengths:
             if "intrinsics" not in batched_inputs[0]:
                 raise AssertionError("SCALE_DEPTH_BY_FOCAL_LENGTHS needs 'intrinsics'")  # dense_depth.py:147
@@ -138,9 +145,47 @@ class DD3DDenseDepth(nn.Module):
             if torch.allclose(K[0], torch.eye(3)):
                 raise ValueError("Intrinsics is Identity.")  # image_list.py:57-62
             plan.in_K.copy_(K.reshape(B, 9), non_blocking=True)
+        return plan, sizes
+
+    def _predict_dense_depth(self, batched_inputs):
+        plan, _ = self._stage(batched_inputs, self.get_plan)
         plan.run()
         plan.check_status()  # one 4-byte read behind the forward (the caller is about to consume the maps anyway); raises and clears
         return [m for m in plan.depth_maps]
+
+    def get_loss_plan(self, B, Hp, Wp):
+        """The loss plan (engine.DenseDepthLossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the
+        prediction plans, under a key of its own."""
+        from dd3d_amd.engine import DenseDepthLossPlan
+        return self._cached_plan(("dense_depth_loss", B, Hp, Wp, self.math), lambda: DenseDepthLossPlan(self, B, Hp, Wp))
+
+    @torch.no_grad()
+    def compute_losses(self, batched_inputs):
+        """The loss dict of the reference's training forward (dense_depth.py:165-171) for a labelled batch: each item carries `image`,
+        `intrinsics` and `depth`, an (Hi, Wi) float map of the image's own size (0 = no return).  Keys `loss_dense_depth_lvl_{l}` in
+        level order, values 0-d float32 tensors on the model's device; NaN at every level when no pixel of the batch is valid.  Needs
+        DD3D.FCOS3D.DEPTH_HEAD.{LOSS_TYPE, LOSS_WEIGHT} in the config (ValueError otherwise).  Every norm layer uses its running
+        statistics; no gradients.  The f16x2 range guard acts as in predict_dense_depth."""
+        from dd3d_amd.engine import relax_arithmetic
+        for i, x in enumerate(batched_inputs):
+            if "depth" not in x:
+                raise ValueError(f"image {i}: compute_losses needs a 'depth' map in every item of the batch")
+        from dd3d_amd.engine.dense_depth_loss import check_depth_maps, dense_depth_loss_config
+        dense_depth_loss_config(self.cfg)  # (config and input errors before a plan is built or an image staged)
+        check_depth_maps([x["depth"] for x in batched_inputs], [(int(x["image"].shape[-2]), int(x["image"].shape[-1])) for x in batched_inputs])
+        while True:
+            try:
+                return self._compute_losses(batched_inputs)
+            except FloatingPointError as e:
+                if not relax_arithmetic(self, e):
+                    raise
+
+    def _compute_losses(self, batched_inputs):
+        plan, sizes = self._stage(batched_inputs, self.get_loss_plan)
+        plan.stage_depth([x["depth"] for x in batched_inputs], sizes, checked=True)  # (compute_losses has validated the maps)
+        plan.run()
+        plan.check_status()
+        return plan.loss_dict()
 
     def forward(self, batched_inputs):
         raise NotImplementedError()  # the reference's eval-mode forward (dense_depth.py:162-163)

@@ -171,3 +171,48 @@ def make_gt_instances(inputs, num_classes, canonical_sizes, seed=2000, n_per_ima
             inst.gt_speeds = torch.from_numpy(sp)
         out.append(inst)
     return out
+
+
+def make_depth_maps(inputs, seed=3000, valid_fraction=0.5, base=None, min_depth=0.1, max_depth=80.0, beta=0.05, below_fraction=0.05,
+                    above_fraction=0.10, gap=1e-3):
+    """Seeded, LiDAR-like sparse ground-truth depth for `inputs` (make_inputs' batch; DD3DDenseDepth.compute_losses reads it as
+    x["depth"]): per image a float32 (Hi, Wi) map that is 0 where there is no return, below `min_depth` on `below_fraction` of the
+    pixels (min_depth - U(0.01, 1): negative values and, for min_depth > 0.01, small positive ones), above `max_depth` on
+    `above_fraction` of them, and inside the range on `valid_fraction` of them.
+
+    Without `base` the in-range values are uniform over the range.  With `base` (per image a map of at least the image's size, e.g. a
+    level of predict_dense_depth) they are base +- d, on pixels whose base value lies far enough inside the range for that (fewer than
+    `valid_fraction` of the pixels when the base leaves the range on many): |d| is below `beta` on about half of them and above it on the
+    others, so that a prediction equal to `base` takes both branches of the smooth-L1, and no pixel has | |d| - beta | < gap -- counted on
+    the float32 difference of the stored value and the base."""
+    out = []
+    for i, x in enumerate(inputs):
+        H, W = int(x["image"].shape[-2]), int(x["image"].shape[-1])
+        n = H * W
+        g = torch.Generator().manual_seed(seed + i)
+        perm = torch.randperm(n, generator=g)
+        rand = lambda k: torch.rand(k, generator=g)
+        n_below, n_above, n_valid = int(below_fraction * n), int(above_fraction * n), int(valid_fraction * n)
+        below, above, rest = perm[:n_below], perm[n_below:n_below + n_above], perm[n_below + n_above:]
+        depth = torch.zeros(n, dtype=torch.float32)
+        depth[below] = min_depth - (0.01 + 0.99 * rand(n_below))
+        depth[above] = max_depth + 0.01 + 40.0 * rand(n_above)
+        if base is None:
+            idx = rest[:n_valid]
+            depth[idx] = min_depth + 0.01 + (max_depth - min_depth - 0.02) * rand(idx.numel())
+        else:
+            b = torch.as_tensor(base[i]).detach().to("cpu", torch.float32)[:H, :W].reshape(-1)
+            assert b.numel() == n, f"base map {i} is smaller than its image"
+            margin = 4.0 * beta + gap
+            ok = (b[rest] > min_depth + margin) & (b[rest] < max_depth - margin)
+            idx = rest[ok][:n_valid]
+            k = idx.numel()
+            slack = 1e-5 + 1e-6 * max(abs(min_depth), abs(max_depth))  # the stored sum is rounded to float32: |d| moves by half an ulp of the base
+            lo = rand(k) * max(beta - gap - slack, 0.0)
+            hi = beta + gap + slack + rand(k) * (3.0 * beta - gap - slack)
+            mag = torch.where(rand(k) < 0.5, lo, hi)
+            sign = torch.where(rand(k) < 0.5, -torch.ones(k), torch.ones(k))
+            depth[idx] = b[idx] + sign * mag
+            assert bool((((depth[idx] - b[idx]).abs() - beta).abs() >= gap).all())
+        out.append(depth.reshape(H, W))
+    return out

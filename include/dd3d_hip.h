@@ -1,5 +1,6 @@
 /*
- * dd3d_hip.h -- C ABI of the MI355X (gfx950) DD3D forward-path library  (libdd3d_hip.so)
+ * dd3d_hip.h -- C ABI of the MI355X (gfx950) DD3D forward-path library  (libdd3d_hip.so): the forward, the evaluators' kernels and the
+ * training losses without gradients (detector: dd3d_loss_*; depth pre-training: dd3d_dense_depth_loss)
  *
  * The reference (TRI-ML/dd3d) has no FFI of its own for this path: it is pure Python and reaches
  * native code only through third-party wheels (cuDNN via torch, torchvision.ops.nms,
@@ -666,6 +667,44 @@ typedef struct dd3d_loss_args {  /* host memory */
 int dd3d_loss_assign(const dd3d_loss_args* args, void* stream);
 int dd3d_loss_terms(const dd3d_loss_args* args, void* stream);
 int dd3d_loss_layout(int64_t* out, int32_t n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Dense-depth training loss of DD3DDenseDepth without gradients (csrc/dense_depth_loss.hip).
+ * Replaces the training branch of DD3DDenseDepth.forward after the head (tridet/modeling/dd3d/dense_depth.py:153-171: aligned_bilinear
+ * of every level, the focal-length scaling, DenseDepthL1Loss per level and the / sqrt(2)^level) and DenseDepthL1Loss.forward
+ * (dense_depth_loss.py:28-36) with tridet/layers/smooth_l1_loss.py.
+ *
+ * One pass over the ground-truth canvas gt [B][Hp][Wp] (f32, images in the top-left corner, 0 elsewhere, 16-byte aligned, Wp a multiple
+ * of 4).  A pixel is valid iff NOT gt < min_depth and NOT gt > max_depth (a NaN is valid and makes every level NaN).  For a valid pixel
+ * and every level l the prediction is the value dd3d_aligned_bilinear_scale(raw[l], ..., h[l], w[l], pitch, stride[l], offset_half,
+ * focal_factor) would write at that pixel -- the same arithmetic, bit for bit; the up-sampled maps are never stored.  The per-pixel term
+ * is 0.5 n^2 for n = |pred - gt| < beta (not divided by beta), n - 0.5 beta otherwise, plain n for beta < 1e-5.
+ *   out[l]   = (loss_weight * (sum_l / count)) / divisor[l]     (f32, in that order; count == 0 gives NaN)
+ *   count[0] = number of valid pixels (exact)
+ * partials: >= min(ceil(B * Hp * Wp / 4 / 256), DD3D_DDL_MAX_BLOCKS) rows of DD3D_DDL_ROW words (per-block sums of the levels, then the
+ * block's count as int32).  Per-block sums in a fixed order, then one single-block launch: no float atomics, the result is the same
+ * bit for bit on every run.  h[l] * stride[l] == Hp and w[l] * stride[l] == Wp for every level, or the call is rejected.
+ * dd3d_dense_depth_loss_layout: sizeof(dd3d_dense_depth_loss_args) and the byte offsets of its fields (layout check of the bindings).
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_DDL_ROW 12
+#define DD3D_DDL_MAX_BLOCKS 1024
+typedef struct dd3d_dense_depth_loss_args {  /* host memory */
+  const float* raw[DD3D_MAX_LEVELS];  /* per level: NHWC f32 predictor map [B][h][w][pitch], channel 0 used (device) */
+  const float* gt;                    /* [B][Hp][Wp] */
+  const float* inv_K;                 /* [B][9] K^-1 of the images; may be NULL when focal_factor <= 0 */
+  float* partials;                    /* [n_partials][DD3D_DDL_ROW] */
+  float* out;                         /* [num_levels] */
+  int64_t* count;                     /* [1] */
+  int32_t h[DD3D_MAX_LEVELS], w[DD3D_MAX_LEVELS], stride[DD3D_MAX_LEVELS];
+  float divisor[DD3D_MAX_LEVELS];     /* f32(sqrt(2)^l), the power taken in float64 on the host */
+  int32_t num_levels, B, Hp, Wp, pitch;
+  int32_t offset_half;                /* FEATURE_LOCATIONS_OFFSET == "half" */
+  int32_t n_partials;
+  float focal_factor;                 /* SCALE_DEPTH_BY_FOCAL_LENGTHS_FACTOR, or <= 0: no focal scaling */
+  float min_depth, max_depth, beta, loss_weight;
+} dd3d_dense_depth_loss_args;
+int dd3d_dense_depth_loss(const dd3d_dense_depth_loss_args* args, void* stream);
+int dd3d_dense_depth_loss_layout(int64_t* out, int32_t n);
 
 #ifdef __cplusplus
 }
