@@ -6,7 +6,7 @@
   plan       PlanBase: buffers, the model's weight store, op helpers, launch / hipGraph capture / replay, the f16x2 range guard
   backbones  DLA / VoVNet-V2 / FPN lowering (mixin)
   forward    ForwardPlan (trunk, heads, select / decode / NMS, the exchange record) and DenseDepthPlan
-  losses     LossPlan (trunk, heads, target assignment, loss terms) and assign_targets (DD3D.prepare_targets)
+  losses     LossPlan (trunk, heads, target assignment, loss terms; grads=True: the loss backward too) and assign_targets (DD3D.prepare_targets)
   dense_depth_loss  DenseDepthLossPlan (DenseDepthPlan's trunk and head, then the fused per-level depth loss) and its GT staging
 
 Everything is re-exported here: `from dd3d_amd.engine import ForwardPlan, ConvOp, choose_tiling, ...` keeps working.

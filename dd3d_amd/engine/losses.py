@@ -1,4 +1,5 @@
-"""Loss engine: target assignment and the training loss dict of DD3D / NuscenesDD3D on the MI355X, without gradients.
+"""Loss engine: target assignment and the training loss dict of DD3D / NuscenesDD3D on the MI355X, and on request the gradient of
+the dict's weighted sum with respect to the head maps (csrc/loss_grads.hip; backward through the convolutions is not implemented).
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -215,11 +216,47 @@ def assign_targets(model, locations, gt_instances, feature_shapes, max_gt=hip.LO
     return t.as_dict(loc, B, len(level_hw), [h * w for h, w in level_hw], model.num_classes)
 
 
+HEAD_KEYS_2D = ("logits", "box2d_reg", "centerness")
+HEAD_KEYS_3D = ("quat", "ctr", "depth", "size", "conf")
+HEAD_KEYS_NUSC = ("attr", "speed")
+BOX3D_COMPONENTS = {"quat": (0, 4), "ctr": (4, 2), "depth": (6, 1), "size": (7, 3), "conf": (10, 1)}  # first component, count (x C3 channels)
+
+
+def fill_grad_args(d_cls, d_b2d, d_b3d, upstream, denoms):
+    """dd3d_loss_grad_args over per-level NHWC gradient buffers (d_b3d None: 2D only)."""
+    g = hip.LossGradArgs()
+    for l in range(len(d_cls)):
+        g.d_cls[l], g.d_box2d[l] = d_cls[l].data_ptr(), d_b2d[l].data_ptr()
+        g.d_box3d[l] = d_b3d[l].data_ptr() if d_b3d is not None else None
+    g.upstream, g.denoms = upstream.data_ptr(), denoms.data_ptr()
+    return g
+
+
+def unpack_head_grads(d_cls, d_b2d, d_b3d, num_classes, num_attr, class_agnostic):
+    """NHWC / pitch gradient buffers -> {key<l>: NCHW tensor} (copies; attr / speed when num_attr > 0, the 3D keys when d_b3d)."""
+    out = {}
+    C_ = num_classes
+    for l in range(len(d_cls)):
+        cl = d_cls[l].permute(0, 3, 1, 2)
+        out[f"logits{l}"] = cl[:, :C_].clone()
+        if num_attr:
+            out[f"attr{l}"], out[f"speed{l}"] = cl[:, C_:C_ + num_attr].clone(), cl[:, C_ + num_attr:C_ + num_attr + 1].clone()
+        b2 = d_b2d[l].permute(0, 3, 1, 2)
+        out[f"box2d_reg{l}"], out[f"centerness{l}"] = b2[:, :4].clone(), b2[:, 4:5].clone()
+        if d_b3d is not None:
+            C3 = 1 if class_agnostic else C_
+            b3 = d_b3d[l].permute(0, 3, 1, 2)
+            for k, (c0, n) in BOX3D_COMPONENTS.items():
+                out[f"{k}{l}"] = b3[:, c0 * C3:(c0 + n) * C3].clone()
+    return out
+
+
 class LossPlan(ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
-    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False):
+    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False):
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
+        self.grads = bool(grads)
         check_loss_config(model.cfg)
         from dd3d_amd.engine.tiling import default_tile_policy
         self.tile_policy = default_tile_policy() or getattr(model, "tile_policy", None) or "latency"  # as ForwardPlan: the forward's own tiles
@@ -274,6 +311,28 @@ class LossPlan(ForwardPlan):
                                dict(kind="loss_assign")))
         self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_terms(C.byref(a), st), "loss_terms"), "loss_terms",
                                dict(kind="loss_terms")))
+        if self.grads:
+            self._loss_grads(a)
+
+    def _loss_grads(self, a):
+        """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
+        more launch, dd3d_loss_backward, behind the loss terms -- still one hipGraph."""
+        like = lambda maps: [torch.zeros_like(m.t) for m in maps]
+        self.d_cls, self.d_b2d = like(self.cls_maps), like(self.b2d_maps)
+        self.d_b3d = like(self.b3d_maps) if self.box3d_on else None
+        self.upstream = torch.ones(hip.LOSS_OUT, dtype=torch.float32, device=self.device)
+        self.grad_denoms = torch.zeros(hip.LOSS_GRAD_DENOMS, dtype=torch.float32, device=self.device)
+        g = fill_grad_args(self.d_cls, self.d_b2d, self.d_b3d, self.upstream, self.grad_denoms)
+        self.grad_args = g
+        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_backward(C.byref(a), C.byref(g), st), "loss_backward"), "loss_backward",
+                               dict(kind="loss_backward")))
+
+    def head_grads(self):
+        """The gradients of the last run as NCHW per-level tensors (copies) under the keys of the reference's head maps."""
+        if not self.grads:
+            raise RuntimeError("this LossPlan was built without grads=True")
+        return unpack_head_grads(self.d_cls, self.d_b2d, self.d_b3d, int(self.model.num_classes), self.loss_args.num_attr if self.nusc else 0,
+                                 bool(self.loss_args.class_agnostic_3d))
 
     def stage_gt(self, gt_instances):
         """Pack the batch's GT into the pinned mirror (plain host stores); `flush_inputs` ships it."""

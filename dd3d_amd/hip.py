@@ -170,6 +170,17 @@ class LossArgs(C.Structure):
     ]
 
 
+LOSS_GRAD_DENOMS = 4
+
+
+class LossGradArgs(C.Structure):
+    """`dd3d_loss_grad_args`."""
+    _fields_ = [
+        ("d_cls", C.c_void_p * MAX_LEVELS), ("d_box2d", C.c_void_p * MAX_LEVELS), ("d_box3d", C.c_void_p * MAX_LEVELS),
+        ("upstream", C.c_void_p), ("denoms", C.c_void_p)
+    ]
+
+
 DDL_ROW, DDL_MAX_BLOCKS = 12, 1024
 DDL_QUADS_PER_BLOCK = 256  # dd3d_dense_depth_loss: a block of 256 threads reads 256 four-pixel groups per sweep
 
@@ -197,7 +208,7 @@ EXPORTS = [
     "dd3d_invert_intrinsics", "dd3d_nms_finalize", "dd3d_bev_nms_aggregate", "dd3d_conv2d_smallc_supported", "dd3d_conv2d_smallc_bf16x3", "dd3d_rotate_iou_eval", "dd3d_d3_box_overlap", "dd3d_image_box_overlap", "dd3d_aligned_bilinear_scale", "dd3d_resize_bilinear_u8",
     "dd3d_format_boxes3d", "dd3d_math_planes", "dd3d_split_planes", "dd3d_maxpool2x2_planes", "dd3d_maxpool2x2_planes_in", "dd3d_upsample2x_add_planes", "dd3d_ese_fused", "dd3d_stem_fused_f16x2", "dd3d_fold_range_flags", "dd3d_pack_readback",
     "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match", "dd3d_loss_assign", "dd3d_loss_terms", "dd3d_loss_layout",
-    "dd3d_dense_depth_loss", "dd3d_dense_depth_loss_layout"
+    "dd3d_dense_depth_loss", "dd3d_dense_depth_loss_layout", "dd3d_loss_backward", "dd3d_loss_grad_layout"
 ]
 
 
@@ -268,6 +279,8 @@ def lib():
     L.dd3d_loss_assign.argtypes = [C.POINTER(LossArgs), C.c_void_p]
     L.dd3d_loss_terms.argtypes = [C.POINTER(LossArgs), C.c_void_p]
     L.dd3d_loss_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_loss_backward.argtypes = [C.POINTER(LossArgs), C.POINTER(LossGradArgs), C.c_void_p]
+    L.dd3d_loss_grad_layout.argtypes = [C.c_void_p, C.c_int32]
     L.dd3d_dense_depth_loss.argtypes = [C.POINTER(DenseDepthLossArgs), C.c_void_p]
     L.dd3d_dense_depth_loss_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:

@@ -119,13 +119,14 @@ class DD3D(nn.Module):
         self._evict_plans()
         return plan
 
-    def get_loss_plan(self, B, Hp, Wp):
-        """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans."""
+    def get_loss_plan(self, B, Hp, Wp, grads=False):
+        """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
+        `grads`: the plan that also runs the loss backward (head-map gradients)."""
         from dd3d_amd.engine.losses import LossPlan
-        key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None))
+        key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + (("grads", ) if grads else ())
         plan = self._plans.pop(key, None)
         if plan is None:
-            plan = LossPlan(self, B, Hp, Wp)
+            plan = LossPlan(self, B, Hp, Wp, grads=True) if grads else LossPlan(self, B, Hp, Wp)
             if self.use_graph:
                 plan.capture()
         self._plans[key] = plan
@@ -285,18 +286,22 @@ class DD3D(nn.Module):
     def _collect_extra(self, r, d, plan):
         pass
 
-    # ------------------------------------------------------------------ training losses (no gradients)
+    # ------------------------------------------------------------------ training losses (gradients: with respect to the head maps only)
     @torch.no_grad()
-    def compute_losses(self, batched_inputs):
+    def compute_losses(self, batched_inputs, head_grads=False):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
         reference: every norm layer uses its running statistics (the head maps are exactly this forward's), one process
-        (reduce_sum is the identity), no gradients."""
+        (reduce_sum is the identity).  With `head_grads` the result is (loss dict, grads): the gradient of the sum of the dict's values
+        with respect to the head maps the losses read, as NCHW per-level tensors under the reference's names (logits<l>, box2d_reg<l>
+        -- post-ReLU --, centerness<l>, quat<l>, ctr<l>, depth<l>, size<l>, conf<l>, attr<l>, speed<l>); there is no backward through
+        the convolutions."""
         from dd3d_amd.engine import relax_arithmetic
         gt = [x["instances"] for x in batched_inputs]
         while True:
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs))
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), grads=True) if head_grads else \
+                self.get_loss_plan(*self.canvas_size(batched_inputs))
             plan.stage_gt(gt)
             self.stage_inputs(batched_inputs, plan=plan)  # (its flush ships the GT too)
             plan.run()
@@ -307,7 +312,8 @@ class DD3D(nn.Module):
                 if not relax_arithmetic(self, e):
                     raise
                 continue
-            return plan.loss_dict(int(rb.counts[0]))
+            losses = plan.loss_dict(int(rb.counts[0]))
+            return (losses, plan.head_grads()) if head_grads else losses
 
     @torch.no_grad()
     def prepare_targets(self, locations, gt_instances, feature_shapes):

@@ -1,6 +1,7 @@
 /*
  * dd3d_hip.h -- C ABI of the MI355X (gfx950) DD3D forward-path library  (libdd3d_hip.so): the forward, the evaluators' kernels and the
- * training losses without gradients (detector: dd3d_loss_*; depth pre-training: dd3d_dense_depth_loss)
+ * training losses (detector: dd3d_loss_*, with the head-map gradients of dd3d_loss_backward; depth pre-training: dd3d_dense_depth_loss,
+ * values only)
  *
  * The reference (TRI-ML/dd3d) has no FFI of its own for this path: it is pure Python and reaches
  * native code only through third-party wheels (cuDNN via torch, torchvision.ops.nms,
@@ -602,7 +603,7 @@ typedef struct dd3d_nusc_match_args {  /* host memory */
 int dd3d_nusc_center_match(const dd3d_nusc_match_args* args, int32_t* match, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Training losses of DD3D / NuscenesDD3D without gradients (csrc/losses.hip).
+ * Training losses of DD3D / NuscenesDD3D (csrc/losses.hip; their head-map gradients: dd3d_loss_backward below).
  * Replaces DD3DTargetPreparer / NuscenesDD3DTargetPreparer (prepare_targets.py:28-235, nuscenes_dd3d.py:24-196), FCOS2DLoss
  * (fcos2d.py:159-239), FCOS3DLoss (fcos3d.py:191-299), DisentangledBox3DLoss (disentangled_box3d_loss.py) and NuscenesLoss
  * (nuscenes_dd3d.py:199-265), single process.
@@ -667,6 +668,33 @@ typedef struct dd3d_loss_args {  /* host memory */
 int dd3d_loss_assign(const dd3d_loss_args* args, void* stream);
 int dd3d_loss_terms(const dd3d_loss_args* args, void* stream);
 int dd3d_loss_layout(int64_t* out, int32_t n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Head-map gradients of the losses above (csrc/loss_grads.hip): d (sum_k upstream[k] * out[k]) / d (cls, box2d, box3d) as
+ * dd3d_loss_terms reads the maps -- logits (+ attr, speed on nuScenes), post-ReLU box2d_reg and centerness, quat / ctr / depth / size /
+ * conf.  The derivative is the one torch autograd gives the reference's FCOS2DLoss, FCOS3DLoss, DisentangledBox3DLoss and NuscenesLoss
+ * (loss_conf3d through the BCE only: the reference detaches its target), with torch's conventions at the non-smooth points: min / max
+ * split a tie in halves, clamp passes 1 on its closed interval, sign(0) = 0, the norms and square roots have derivative 0 at 0.
+ *
+ * dd3d_loss_backward runs after dd3d_loss_assign and dd3d_loss_terms on the same `args` and stream; it reads the labels, the targets,
+ *   flags, out[10] (positive count), out[11] (loss_denom) and the partials slab (the attribute and speed denominators, recomputed in the
+ *   finalize launch's summation order into denoms[0..2]).  One thread per target writes the complete rows of its location in the three
+ *   gradient maps, channels [0, nch): zeros for a background row and for the 3D channels of classes other than the label; the pad words
+ *   up to the pitch stay untouched.  No word has two writers: no memset is needed, there is no atomic on a float, and two runs agree
+ *   bit for bit.  denoms: 4 words of device scratch; after the call the int32 at denoms[3] is 0 unless the value part of the
+ *   backward's decode differed from the forward's in some positive (it never should: a self-check of the two statements).
+ * dd3d_loss_grad_layout: sizeof(dd3d_loss_grad_args) and the byte offsets of its fields (layout check of the bindings; host only).
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_LOSS_GRAD_DENOMS 4
+typedef struct dd3d_loss_grad_args {      /* host memory */
+  float* d_cls[DD3D_MAX_LEVELS];          /* same NHWC layout and pitch as dd3d_loss_args.cls / box2d / box3d */
+  float* d_box2d[DD3D_MAX_LEVELS];
+  float* d_box3d[DD3D_MAX_LEVELS];        /* NULL where box3d[l] is NULL */
+  const float* upstream;                  /* device, DD3D_LOSS_OUT floats: d total / d out[k], k as in out[] (0..9 used) */
+  float* denoms;                          /* device scratch, DD3D_LOSS_GRAD_DENOMS words */
+} dd3d_loss_grad_args;
+int dd3d_loss_backward(const dd3d_loss_args* args, const dd3d_loss_grad_args* grads, void* stream);
+int dd3d_loss_grad_layout(int64_t* out, int32_t n);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense-depth training loss of DD3DDenseDepth without gradients (csrc/dense_depth_loss.hip).
