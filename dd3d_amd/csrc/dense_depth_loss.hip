@@ -4,14 +4,16 @@
 //
 //   dense_depth_loss_kernel    one pass over the ground-truth canvas, four pixels (one 16-byte load) per thread and iteration.  For a
 //                              valid pixel every level's prediction is evaluated in place: four bilinear taps into the level's raw
-//                              predictor map (a few hundred KB over all levels: cache resident), the arithmetic of
-//                              aligned_bilinear_scale_kernel (aux_kernels.hip) restated operation for operation.  A thread keeps one sum
+//                              predictor map (a few hundred KB over all levels: cache resident), aligned_bilinear_at
+//                              (aligned_bilinear.h), which aligned_bilinear_scale_kernel (aux_kernels.hip) writes out.  A thread keeps one sum
 //                              per level and one integer count; per-block sums in a fixed tree order go to a slab.
 //   dense_depth_finalize_kernel one block: the slab summed in a fixed order, then mean, weight and the per-level divisor.
 // No float atomics: two runs on the same inputs agree bit for bit.
 #include <math.h>
 
+#include "aligned_bilinear.h"
 #include "common.h"
+#include "smooth_l1.h"
 
 DD3D_NOTE_BUILD_FLAGS
 
@@ -25,48 +27,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 struct DenseDepthLossK {
   dd3d_dense_depth_loss_args a;
 };
-
-// Value of aligned_bilinear_scale_kernel's output pixel (b, y, x) for one level.  The statements are that kernel's, under the same
-// contraction settings (the translation unit's default, the source coordinate under contract(off)), so the compiler makes the same
-// arithmetic of them: tests/test_dense_depth_loss_gpu.py compares the two bit for bit, pixel by pixel.
-__device__ __forceinline__ float aligned_bilinear_at(const float* __restrict__ src, const float* __restrict__ inv_K, int b, int y, int x, int h,
-                                                     int w, int pitch, int f, int half, float factor) {
-  const float scale = (float)h / (float)(f * h);  // (in - 1) / (out - 1) of the padded (h+1) -> (f*h+1) resize, = 1/f
-  const float scale_w = (float)w / (float)(f * w);
-  const int ys = half ? max(y - f / 2, 0) : y, xs = half ? max(x - f / 2, 0) : x;
-  float ry, rx;
-  {
-    // the source coordinate is rounded to f32 before its fraction is taken (see aligned_bilinear_scale_kernel)
-#pragma clang fp contract(off)
-    ry = scale * (float)ys;
-    rx = scale_w * (float)xs;
-  }
-  const int y0 = (int)ry, x0 = (int)rx;  // < h, w: ys <= f*h - 1 and the canvas is far below 2^23 pixels a side (the entry point checks)
-  const float ly = ry - (float)y0, lx = rx - (float)x0;
-  const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);  // row / column h, w of the padded map replicate h-1, w-1
-  const float* p = src + (long)b * h * w * pitch;
-  const float v00 = p[((long)y0 * w + x0) * pitch], v01 = p[((long)y0 * w + x1) * pitch];
-  const float v10 = p[((long)y1 * w + x0) * pitch], v11 = p[((long)y1 * w + x1) * pitch];
-  float v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
-  if (factor > 0.f) {
-    const float k0 = inv_K[9 * b], k4 = inv_K[9 * b + 4];
-    v = v / (sqrtf(k0 * k0 + k4 * k4) * factor);
-  }
-  return v;
-}
-
-// tridet/layers/smooth_l1_loss.py:57-74 (the smooth_l1 of losses.hip): 0.5 n^2 below beta (NOT / beta), n - 0.5 beta above; plain L1 for
-// beta < 1e-5.  Every operation rounded on its own, like the reference's tensor ops; so is the running sum.
-__device__ __forceinline__ float add_smooth_l1(float acc, float x, float y, float beta) {
-#pragma clang fp contract(off)
-  const float n = fabsf(x - y);
-  float t;
-  if (beta < 1e-5f)
-    t = n;
-  else
-    t = n < beta ? 0.5f * (n * n) : n - 0.5f * beta;
-  return acc + t;
-}
 
 __global__ __launch_bounds__(DT) void dense_depth_loss_kernel(const DenseDepthLossK P) {
   const dd3d_dense_depth_loss_args& a = P.a;
@@ -94,7 +54,10 @@ __global__ __launch_bounds__(DT) void dense_depth_loss_kernel(const DenseDepthLo
         for (int l = 0; l < DD3D_MAX_LEVELS; ++l) {
           if (l < L) {
             const float v = aligned_bilinear_at(a.raw[l], a.inv_K, b, y, xq + e, a.h[l], a.w[l], a.pitch, a.stride[l], a.offset_half, factor);
-            sum[l] = add_smooth_l1(sum[l], v, gt, a.beta);
+            {  // the running sum rounded on its own, like the smooth-L1's operations (smooth_l1.h) and the reference's tensor ops
+#pragma clang fp contract(off)
+              sum[l] = sum[l] + smooth_l1(v, gt, a.beta);
+            }
           }
         }
       }

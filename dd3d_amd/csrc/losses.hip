@@ -10,6 +10,8 @@
 //                        attribute cross entropy and the speed loss (fvcore's smooth-L1, the corners use tridet's).  Per-block partial sums of DD3D_LOSS_TERMS terms in a fixed tree
 //                        order go to a slab.
 //   loss_finalize_kernel one block: the slab summed in a fixed order, then the denominators and the loss values.
+// The pieces the backward needs as well (target indexing, focal pieces, GIoU, corners, renormalisation, entangled error, the slab's column
+// sum) are in loss_common.h, GIoU and the 3D chain as templates over the scalar type: loss_grads.hip instantiates them on dual numbers.
 // No float atomics anywhere: the result is the same bit for bit on every run.
 #pragma clang fp contract(off)
 #include <math.h>
@@ -116,12 +118,9 @@ __global__ __launch_bounds__(LT) void loss_terms_kernel(const LossK P) {
 #pragma unroll
   for (int k = 0; k < DD3D_LOSS_TERMS; ++k) t[k] = 0.f;
   if (n < N) {
-    int l = 0;
-    while (l + 1 < a.num_levels && n >= (long)a.B * a.loc_off[l + 1]) ++l;
-    const int HW = a.H[l] * a.W[l];
-    const long rr = n - (long)a.B * a.loc_off[l];
-    const int b = (int)(rr / HW), p = (int)(rr - (long)b * HW);
-    const long pix = (long)b * HW + p;
+    const TargetIndex ti = target_index(a, n);
+    const int l = ti.l, b = ti.b, p = ti.p;
+    const long pix = ti.pix;
     const int C = a.num_classes;
     const int label = a.labels[n];
     const bool pos = label != C;
@@ -131,12 +130,9 @@ __global__ __launch_bounds__(LT) void loss_terms_kernel(const LossK P) {
     for (int c = 0; c < C; ++c) {
       const float xv = cl[c];
       const float tv = (pos && c == label) ? 1.f : 0.f;
-      const float pr = 1.0f / (1.0f + expf(-xv));
-      const float ce = bce_logits(xv, tv);
-      const float p_t = pr * tv + (1.f - pr) * (1.f - tv);
-      const float m = 1.f - p_t;
-      const float mod = a.focal_gamma == 2.0f ? m * m : powf(m, a.focal_gamma);
-      float lv = ce * mod;
+      FocalPieces f;
+      focal_pieces(xv, tv, a.focal_gamma, f);
+      float lv = f.ce * f.mod;
       if (a.focal_alpha >= 0.f) lv = (a.focal_alpha * tv + (1.f - a.focal_alpha) * (1.f - tv)) * lv;
       fs += lv;
     }
@@ -147,22 +143,7 @@ __global__ __launch_bounds__(LT) void loss_terms_kernel(const LossK P) {
       t[T_CTR] = ct;
       const float* pb = a.box2d[l] + pix * a.b2d_pitch;
       const float* tg = a.box2d_reg + 4 * n;
-      {  // IOULoss "giou" (iou_loss.py:20-71), weighted by the centerness target
-        const float pl = pb[0], pt = pb[1], pr_ = pb[2], pbm = pb[3];
-        const float tl = tg[0], tt = tg[1], tr = tg[2], tb = tg[3];
-        const float target_area = (tl + tr) * (tt + tb);
-        const float pred_area = (pl + pr_) * (pt + pbm);
-        const float w_int = fminf(pl, tl) + fminf(pr_, tr);
-        const float h_int = fminf(pbm, tb) + fminf(pt, tt);
-        const float gw = fmaxf(pl, tl) + fmaxf(pr_, tr);
-        const float gh = fmaxf(pbm, tb) + fmaxf(pt, tt);
-        const float ac_union = gw * gh;
-        const float area_int = w_int * h_int;
-        const float area_union = target_area + pred_area - area_int;
-        const float ious = (area_int + 1.0f) / (area_union + 1.0f);
-        const float gious = ious - (ac_union - area_union) / ac_union;
-        t[T_GIOU] = (1.f - gious) * ct;
-      }
+      t[T_GIOU] = (1.f - giou(pb, tg)) * ct;  // IOULoss "giou", weighted by the centerness target
       t[T_CTRBCE] = bce_logits(pb[4], ct);
       if (a.box3d[l] != nullptr) {
         const int C3 = a.class_agnostic_3d ? 1 : C, c3 = a.class_agnostic_3d ? 0 : label;
@@ -172,11 +153,8 @@ __global__ __launch_bounds__(LT) void loss_terms_kernel(const LossK P) {
         const float* Kp = a.inv_K + 9 * b;
         const Box3dDecodeParams dp{a.scale_depth_by_focal, a.depth_is_distance, a.allocentric, a.focal_factor, a.min_depth, a.max_depth};
         const Box3dDecoded d = decode_box3d(pm, C3, c3, lx, ly, Kp, a.canon_sizes + 3 * label, dp);
-        float q[4] = {d.q0, d.q1, d.q2, d.q3};
-        if (a.allocentric && *a.flags) {
-          const float dn = fmaxf(d.qn, DECODE_QEPS);
-          q[0] /= dn, q[1] /= dn, q[2] /= dn, q[3] /= dn;
-        }
+        float q[4];
+        decoded_quat(d, a.allocentric, a.flags, q);
         const float pc[2] = {d.cx, d.cy}, ps[3] = {d.s0, d.s1, d.s2};
         const float* tb3 = a.box3d_t + n * DD3D_LOSS_BOX3D_FIELDS;  // quat 0-3, proj_ctr 4-5, depth 6, size 7-9, K^-1 10-18
         const float* tK = tb3 + 10;
@@ -190,12 +168,7 @@ __global__ __launch_bounds__(LT) void loss_terms_kernel(const LossK P) {
         t[T_DEPTH] = corner_group_loss(tc, tb3, tb3 + 4, d.depth, tb3 + 7, tK, beta) * ct;
         t[T_SIZE] = corner_group_loss(tc, tb3, tb3 + 4, tb3[6], ps, tK, beta) * ct;
         // entangled L1 of the whole prediction (its own K^-1: the image's) -> conf target -> BCE (fcos3d.py:289-295)
-        float ec[24];
-        box_corners(q, pc, d.depth, ps, Kp, ec);
-        float es = 0.f;
-#pragma unroll
-        for (int e = 0; e < 24; ++e) es += fabsf(tc[e] - ec[e]);
-        const float err = es / 24.f;
+        const float err = entangled_error(tc, q, pc, d.depth, ps, Kp);
         const float conf_t = expf(-1.f / a.conf3d_temperature * err);
         t[T_CONF] = bce_logits(pm[10 * C3 + c3], conf_t) * ct;
       }
@@ -244,18 +217,7 @@ __global__ __launch_bounds__(LT) void loss_finalize_kernel(const LossK P, int nb
   const dd3d_loss_args& a = P.a;
   __shared__ float red[LT];
   __shared__ float S[DD3D_LOSS_TERMS];
-  for (int k = 0; k < DD3D_LOSS_TERMS; ++k) {
-    float s = 0.f;
-    for (int r = threadIdx.x; r < nblocks; r += LT) s += a.partials[(long)r * DD3D_LOSS_TERMS + k];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = LT / 2; h > 0; h >>= 1) {
-      if (threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) S[k] = red[0];
-    __syncthreads();
-  }
+  for (int k = 0; k < DD3D_LOSS_TERMS; ++k) column_sum(a.partials, nblocks, k, red, &S[k]);
   if (threadIdx.x != 0) return;
   float* o = a.out;
   const float npos = S[T_NPOS];
