@@ -92,8 +92,11 @@ __global__ __launch_bounds__(LT) void loss_backward_kernel(const LossK P, const 
     const float tv = (pos && c == label) ? 1.f : 0.f;
     FocalPieces f;
     focal_pieces(xv, tv, a.focal_gamma, f);
-    // d(ce m^gamma)/dx with dce/dx = p - t and dm/dx = (1 - 2t) p (1 - p)
-    const float dmod = a.focal_gamma == 2.0f ? 2.0f * f.m : a.focal_gamma * powf(f.m, a.focal_gamma - 1.0f);
+    // d(ce m^gamma)/dx with dce/dx = p - t and dm/dx = (1 - 2t) p (1 - p).  m is exactly 0 in float32 for a confidently classified
+    // logit (beyond about +-17): d(m^0)/dm is 0 there as everywhere (torch's pow backward; not 0 * 0^-1 = NaN), gamma >= 1 gives a
+    // finite power, and 0 < gamma < 1 gives gamma * 0^(gamma - 1) = inf and a non-finite row, in torch as well: the host refuses
+    // that range (engine/losses.py check_loss_config)
+    const float dmod = a.focal_gamma == 2.0f ? 2.0f * f.m : a.focal_gamma == 0.0f ? 0.0f : a.focal_gamma * powf(f.m, a.focal_gamma - 1.0f);
     float dv = (f.pr - tv) * f.mod + f.ce * (dmod * ((1.f - 2.f * tv) * (f.pr * (1.f - f.pr))));
     if (a.focal_alpha >= 0.f) dv = (a.focal_alpha * tv + (1.f - a.focal_alpha) * (1.f - tv)) * dv;
     dcl[c] = kf * dv;

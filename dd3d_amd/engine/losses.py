@@ -65,6 +65,12 @@ def check_loss_config(cfg):
     loc = str(cfg.DD3D.FCOS2D.LOSS.LOC_LOSS_TYPE)
     if loc != "giou":
         raise ValueError(f"DD3D.FCOS2D.LOSS.LOC_LOSS_TYPE = {loc!r}: the loss engine implements 'giou' (every reference config's choice) only")
+    gamma = float(cfg.DD3D.FCOS2D.LOSS.GAMMA)
+    if not (gamma == 0.0 or gamma >= 1.0):
+        # (1 - p_t)^gamma at 1 - p_t == 0, which float32 reaches for any logit beyond about +-17: infinite below 0, and between 0 and 1
+        # its derivative gamma * 0^(gamma - 1) is, which makes the location's logit gradients non-finite (in torch autograd as well)
+        raise ValueError(f"DD3D.FCOS2D.LOSS.GAMMA = {gamma}: the focal loss needs GAMMA == 0 or GAMMA >= 1 (below 0 the loss, and between 0 "
+                         "and 1 its gradient, is not finite at a confidently classified logit)")
 
 
 def pack_gt(gt_instances, max_gt, box3d, nusc, num_attr, num_classes):

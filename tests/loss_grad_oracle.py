@@ -55,7 +55,9 @@ def flat_family(grads, key, p):
 
 def near_kink(maps, targets, inv_K, p, margin=KINK_MARGIN):
     """Boolean mask over the positives (the order of targets["pos_inds"]): True where the positive lies within `margin` of a point
-    where the loss is not differentiable or jumps -- a disentangled corner residual at beta, the speed residual at 0.05, a GIoU side
+    where the loss is not differentiable or jumps -- a disentangled corner residual at beta (at 0 for beta < 1e-5, plain L1; only a
+    residual the prediction can move counts: a corner's z does not depend on the projected centre when the third row of K^-1 is
+    (0, 0, 1), so the proj_ctr group's z residuals are 0 whatever the prediction, with a zero tangent), the speed residual at 0.05, a GIoU side
     equal to its target, the decoded depth on a clamp bound (relative), the two largest q_abs of matrix_to_quaternion equal.
     Evaluated in float64 on the float32 inputs."""
     f64 = torch.float64
@@ -83,9 +85,14 @@ def near_kink(maps, targets, inv_K, p, margin=KINK_MARGIN):
         tb = t["box3d"][pos]
         tq, tc, td, ts, tK = tb[:, 0:4], tb[:, 4:6], tb[:, 6:7], tb[:, 7:10], tb[:, 10:19].reshape(-1, 3, 3)
         target_corners = LO._corners(tq, tc, td, ts, tK)
-        for qq, cc, dd, ss in ((b["quat"], tc, td, ts), (tq, b["proj_ctr"], td, ts), (tq, tc, b["depth"], ts), (tq, tc, td, b["size"])):
-            res = (LO._corners(qq, cc, dd, ss, tK) - target_corners).abs().reshape(n, 24)
-            mask |= ((res - p["beta"]).abs() <= margin).any(1)
+        kink_at = p["beta"] if p["beta"] >= 1e-5 else 0.0
+        ctr_moves_z = (tK[:, 2, :2] != 0).any(1)  # tvec z = (K20 u + K21 v + K22) * depth
+        for grp, (qq, cc, dd, ss) in enumerate(((b["quat"], tc, td, ts), (tq, b["proj_ctr"], td, ts), (tq, tc, b["depth"], ts), (tq, tc, td, b["size"]))):
+            res = (LO._corners(qq, cc, dd, ss, tK) - target_corners).abs().reshape(n, 8, 3)
+            near = (res - kink_at).abs() <= margin
+            if grp == 1:
+                near[:, :, 2] &= ctr_moves_z[:, None]
+            mask |= near.reshape(n, 24).any(1)
         # the depth before its clamp (fcos3d.py:36-42)
         dep = d.reshape(-1)
         if p["scale_depth"]:

@@ -128,6 +128,73 @@ def test_kink_counts_of_the_gpu_cases_stay_under_the_cap():
         assert bool(case.kink[tie]) and bool(case.kink[exact])  # on a non-smooth point by construction
 
 
+def _finite(d):
+    return all(bool(torch.isfinite(v).all()) for v in d.values())
+
+
+@pytest.mark.parametrize("name,key", GC.SETTINGS_ROWS)
+def test_settings_rows_are_not_vacuous(name, key):
+    """Pins the GT seed of every (case, settings row) the GPU tests run: enough positives, few of them under the kink mask, finite
+    float64 / float32 reference gradients and a finite loss dict."""
+    case = GC.settings_case(name, key)
+    n, k = case.num_pos, int(case.kink.sum())
+    fin64, fin32, finl = _finite(case.ref(torch.float64)), _finite(case.ref(torch.float32)), _finite(case.losses()) and _finite(case.losses(torch.float64))
+    print(f"[settings] {name} {key}: positives {n}, masked {k} ({100.0 * k / max(n, 1):.2f} %), finite g64 {fin64} g32 {fin32} losses {finl}")
+    assert n > 20 and k <= GC.KINK_CAP * n, (name, key, n, k)
+    assert fin64 and fin32 and finl
+    over = GC.SETTINGS[key]["DD3D"]
+    if "FCOS2D" in over:  # the row's values reached the oracle's settings
+        assert (case.p["alpha"], case.p["gamma"]) == (over["FCOS2D"]["LOSS"].get("ALPHA", 0.25), over["FCOS2D"]["LOSS"]["GAMMA"])
+    if "nusc" in name:
+        assert (case.p["w_attr"], case.p["w_speed"]) == (0.4, 2.5)
+
+
+def test_proj_ctr_z_residuals_do_not_count_as_kinks():
+    """Plain L1 (beta < 1e-5) has its kink at residual 0, and the proj_ctr group's eight z residuals are 0 whatever the prediction:
+    counting them would mask every positive.  With them skipped the row is under the cap; moving a z residual by hand still masks."""
+    case = GC.settings_case(GC.SETTINGS_KITTI, "beta_tiny")
+    assert case.p["beta"] < 1e-5 and int(case.kink.sum()) <= GC.KINK_CAP * case.num_pos
+    # the structural zeros are there: the group's z residuals of every positive are exactly 0
+    t, pos = GO._cast(case.targets, torch.float64), case.targets["pos_inds"]
+    tb = t["box3d"][pos]
+    tq, tc, td, ts, tK = tb[:, 0:4], tb[:, 4:6], tb[:, 6:7], tb[:, 7:10], tb[:, 10:19].reshape(-1, 3, 3)
+    moved = LO._corners(tq, tc + 3.0, td, ts, tK) - LO._corners(tq, tc, td, ts, tK)
+    assert float(moved[..., 2].abs().max()) == 0.0 and float(moved[..., :2].abs().min()) > 0.0
+    # a K^-1 whose third row reaches the centre makes those residuals count again
+    skew = case.inv_K.clone()
+    skew[:, 2, 0] = 1e-9
+    t2 = dict(case.targets)
+    t2["box3d"] = case.targets["box3d"].clone()
+    t2["box3d"][:, 10:19] = skew[case.targets["im_inds"]].reshape(-1, 9)
+    assert int(GO.near_kink(case.maps, t2, case.inv_K, case.p).sum()) > GC.KINK_CAP * case.num_pos
+
+
+def test_saturated_and_poisoned_cases_on_the_cpu():
+    for hw in ((4, 4), (1, 257)):
+        for gamma in GC.SATURATED_GAMMAS:
+            case = GC.handmade_case(*hw, gamma=gamma)
+            assert case.num_pos == len(case.specs) == 6 and case.p["gamma"] == gamma
+            lg = LO.flat(case.maps, "logits", 1, case.p["num_classes"])
+            bg = case.targets["labels"] == case.p["num_classes"]
+            assert int((lg[bg] == -60.0).all(1).sum()) == 2 and int((lg[~bg] == 60.0).sum()) == 2 and int((lg[~bg] == -60.0).sum()) == 1
+            assert _finite(case.ref(torch.float64)) and _finite(case.ref(torch.float32)) and _finite(case.losses(torch.float64))
+    for name in GC.POISONED_CASES:
+        case, clean = GC.poisoned_case(name), GC.golden_case(name)
+        j = case.poisoned
+        n = int(case.targets["pos_inds"][j])
+        assert not bool(clean.kink[j]) and 64 <= n % 256 < 192 and ("nusc" not in name or int(case.targets["im_inds"][n]) != 0)
+        ref = case.losses(torch.float64)
+        nan = {k for k, v in ref.items() if bool(torch.isnan(v))}
+        assert nan == {"loss_conf3d", "loss_box3d_quat"}, nan
+        g64 = case.ref(torch.float64)
+        for fam in GO.families(case.p):
+            g = GO.flat_family(g64, fam, case.p)
+            rest = torch.ones(g.shape[0], dtype=torch.bool)
+            rest[n] = False
+            assert bool(torch.isfinite(g[rest]).all()), (name, fam)
+            assert bool(torch.isnan(g[n]).any()) == (fam in ("quat", "ctr", "conf")), (name, fam)
+
+
 def test_loss_grad_args_layout_matches_header(hiplib, tmp_path):
     from dd3d_amd import hip
     cls = hip.LossGradArgs

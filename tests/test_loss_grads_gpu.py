@@ -1,7 +1,9 @@
 """Loss backward on the MI355X (csrc/loss_grads.hip, engine.LossPlan(grads=True), dd3d_amd.losses.FusedDD3DLoss): dd3d_loss_backward at
 its C-ABI seam on the committed reference head maps and on hand-built non-smooth points, against the float64 autograd of the CPU oracle
 (tests/loss_grad_oracle.py) and the reference's own loss modules (tests/golden/loss_grads_*.npz); sentinel-framed buffers, upstream
-weights, batches without positives, determinism, DD3D.compute_losses(head_grads=True) end to end and the autograd entry point.
+weights, batches without positives, determinism, DD3D.compute_losses(head_grads=True) end to end and the autograd entry point; the same
+seam at every row of loss_grad_cases.SETTINGS (each loss setting away from its released value), on saturated logits and on the
+renormalised decode path.
 
 The bar of a family in a case is 8 * max(d32, 2^-23 * max|g64|): d32 is the deviation of the oracle's float32 autograd from its float64
 autograd, computed here on the CPU (tests/loss_grad_oracle.bar).  Positives within 1e-4 of a non-smooth point (loss_grad_oracle.near_kink)
@@ -15,6 +17,7 @@ import torch
 
 from tests import loss_grad_cases as GC
 from tests import loss_grad_oracle as GO
+from tests import loss_oracle as LO
 from tests.test_losses_gpu import GOLDEN_CASES
 
 pytestmark = pytest.mark.gpu
@@ -99,12 +102,19 @@ def run_seam(case, upstream=None, backward=True, maps=None):
     return res
 
 
-def check_against_oracle(case, got, upstream=None, what="", report=None):
-    """Every family within its bar of the float64 autograd off the kink mask; masked rows finite."""
+def check_against_oracle(case, got, upstream=None, what="", report=None, nan_row=None):
+    """Every family within its bar of the float64 autograd off the kink mask; masked rows finite.  `nan_row`: a target whose rows must
+    be NaN exactly where the float64 autograd's are; it is left out of the bar (d32 and max|g64| over the other rows)."""
     g64, g32 = case.ref(torch.float64, upstream), case.ref(torch.float32, upstream)
     keep = case.keep_rows()
     for fam in GO.families(case.p):
         a, b, k = GO.flat_family(g64, fam, case.p), GO.flat_family(g32, fam, case.p), GO.flat_family(got, fam, case.p)
+        if nan_row is not None:
+            assert torch.equal(torch.isnan(k[nan_row]), torch.isnan(a[nan_row])) and bool(torch.isfinite(k[nan_row][~torch.isnan(a[nan_row])]).all()), (what, fam)
+            rest = torch.ones(a.shape[0], dtype=torch.bool)
+            rest[nan_row] = False
+            keep = keep & rest
+            a, b, k = (torch.where(rest[:, None], x, torch.zeros_like(x)) for x in (a, b, k))
         assert bool(torch.isfinite(k).all()), (what, fam)
         bar, d32, gmax = GO.bar(a, b, keep)
         dev = float((k.double() - a)[keep].abs().max())
@@ -266,9 +276,9 @@ def test_no_positives_and_an_image_without_gt(hiplib):
             assert float(GO.flat_family(got["grads"], fam, one.p)[second].abs().max()) == 0.0, fam
 
 
-def _model(exp, weights):
+def _model(exp, weights, overrides=None):
     from dd3d_amd.synthetic import load_calib, make_state_dict
-    m = GC.cpu_model(exp)
+    m = GC.cpu_model(exp, overrides)
     m.load_state_dict(make_state_dict(m, calib=load_calib(weights)))
     return m.to("cuda").eval()
 
@@ -276,9 +286,19 @@ def _model(exp, weights):
 @pytest.mark.parametrize("exp,weights,B,H,W,ds", [("dd3d_kitti_dla34", "dla34_kitti", 2, 128, 384, "kitti"),
                                                    ("dd3d_nusc_dla34", "dla34_nusc", 6, 128, 224, "nusc")])
 def test_compute_losses_head_grads_end_to_end_and_determinism(hiplib, exp, weights, B, H, W, ds):
+    _end_to_end(exp, weights, B, H, W, ds)
+
+
+def test_compute_losses_head_grads_end_to_end_away_from_the_released_settings(hiplib):
+    """The captured graph carries non-default settings: the powf branch without alpha, beta 0.5, temperature 3 and other weights."""
+    over = GC.merged(GC.SETTINGS["gamma1.5_alpha_off"], GC.SETTINGS["beta0.5_T3_weights"])
+    _end_to_end("dd3d_kitti_dla34", "dla34_kitti", 2, 128, 384, "kitti", over)
+
+
+def _end_to_end(exp, weights, B, H, W, ds, overrides=None):
     from dd3d_amd.synthetic import make_gt_instances, make_inputs
     from tests.test_losses_gpu import _maps_nchw
-    model = _model(exp, weights)
+    model = _model(exp, weights, overrides)
     nusc = hasattr(model, "attr_logits")
     inputs = make_inputs(B, H, W, dataset=ds)
     gt = make_gt_instances(inputs, model.num_classes, model.cfg.DD3D.FCOS3D.CANONICAL_BOX3D_SIZES,
@@ -291,9 +311,13 @@ def test_compute_losses_head_grads_end_to_end_and_determinism(hiplib, exp, weigh
     plan = model.get_loss_plan(*model.canvas_size(inputs), grads=True)
     assert [op.name for op in plan.ops][-2:] == ["loss_terms", "loss_backward"]
     assert int(plan.grad_denoms.cpu().view(torch.int32)[3]) == 0
-    case = GC.Case(GC.cpu_model(exp), _maps_nchw(plan), gt, [(f.H, f.W) for f in plan.features], plan.inv_K.view(-1, 3, 3).cpu())
+    case = GC.Case(GC.cpu_model(exp, overrides), _maps_nchw(plan), gt, [(f.H, f.W) for f in plan.features], plan.inv_K.view(-1, 3, 3).cpu())
     assert int(case.kink.sum()) <= GC.KINK_CAP * case.num_pos and case.num_pos > 20
-    check_against_oracle(case, {k: v.cpu() for k, v in grads.items()}, what="e2e:" + ds)
+    check_against_oracle(case, {k: v.cpu() for k, v in grads.items()}, what="e2e:" + ds + (":settings" if overrides else ""))
+    if overrides:  # the settings reached the loss values as well
+        from tests.test_losses_gpu import _close
+        _close({k: v.cpu() for k, v in losses.items()}, case.losses(), 5e-6)
+        assert (case.p["gamma"], case.p["alpha"], case.p["beta"], case.p["temperature"]) == (1.5, -1.0, 0.5, 3.0)
     # two calls agree bit for bit; the captured graph equals launch-by-launch execution
     _, again = model.compute_losses(inputs, head_grads=True)
     assert all(torch.equal(again[k], grads[k]) for k in grads)
@@ -301,6 +325,69 @@ def test_compute_losses_head_grads_end_to_end_and_determinism(hiplib, exp, weigh
     model.invalidate_plans()
     l2, eager = model.compute_losses(inputs, head_grads=True)
     assert all(torch.equal(eager[k], grads[k]) for k in grads) and all(torch.equal(l2[k], plain[k]) for k in plain)
+
+
+# ---------------------------------------------------------------------------------------------- away from the released settings
+@pytest.mark.parametrize("name,key", GC.SETTINGS_ROWS)
+def test_backward_at_seam_away_from_the_released_settings(hiplib, name, key):
+    case = GC.settings_case(name, key)
+    got = run_seam(case)
+    assert got["num_pos"] == case.num_pos > 20 and int(case.kink.sum()) <= GC.KINK_CAP * case.num_pos and got["renorm"] == 0
+    assert got["primal_mismatch"] == 0
+    check_against_oracle(case, got["grads"], what=f"{name}:{key}")
+
+
+@pytest.mark.parametrize("gamma", GC.SATURATED_GAMMAS)
+@pytest.mark.parametrize("H,W", [(4, 4), (1, 257)])
+def test_backward_on_saturated_logits(hiplib, H, W, gamma):
+    """Logits of +-60 (1 - p_t exactly 0 or 1 in float32) on positives and on whole background rows: every gradient word finite and
+    within the bar.  At gamma 0 the derivative of m^0 is 0, as torch's pow gives it, not 0 * 0^-1."""
+    case = GC.handmade_case(H, W, gamma=gamma)
+    got = run_seam(case)
+    assert got["num_pos"] == len(case.specs) == case.num_pos and got["primal_mismatch"] == 0
+    assert all(bool(torch.isfinite(v).all()) for v in got["grads"].values())
+    check_against_oracle(case, got["grads"], what=f"saturated{H}x{W}:gamma{gamma}")
+    lg, g64 = GO.flat_family(got["grads"], "logits", case.p), GO.flat_family(case.ref(), "logits", case.p)
+    sat = LO.flat(case.maps, "logits", 1, case.p["num_classes"]).abs() == 60.0
+    assert int(sat.sum()) == 3 + 2 * case.p["num_classes"]
+    # the confidently wrong logits carry a gradient of the order of 1 / num_pos, the confidently right ones next to none
+    assert float(lg[sat].abs().max()) > 0.1 and float(g64[sat].abs().max()) > 0.1 and float(lg[sat].abs().min()) <= 1e-20
+
+
+@pytest.mark.parametrize("name", GC.POISONED_CASES)
+def test_backward_on_the_renormalised_path(hiplib, name):
+    """The batch-wide renormalisation of the allocentric decode (geometry.py:48-53; loss_assign_kernel's flags word, the `*flags`
+    branch of loss_common.h::decoded_quat on floats in the forward and on dual numbers here), reached with finite numbers: one
+    positive's quaternion is all zeros (loss_grad_cases.poisoned_case), that box decodes to NaN and sets the trigger, and every other
+    positive of the batch is divided by its clamped norm.
+
+    Proves: the trigger fires (flags 1; 0 on the clean case) and is batch-wide; the float and the dual instantiation agree bit for bit
+    under it (primal_mismatch 0, NaN counted equal to NaN); the poisoned target's rows are NaN exactly where the float64 autograd's
+    are (quat, ctr, conf), and every other row is finite and within the usual bar of the float64 autograd, which takes its own
+    renormalisation branch (allclose on a NaN norm is false).
+    Does not prove: that the derivative of the division is right in detail.  A proper rotation's quaternion has norm 1 whatever the
+    inputs, so dividing by the norm moves the float64 gradient by about 1e-17 of its size (measured on the CPU); a subtly wrong
+    derivative of that division cannot be told from a correct one here."""
+    case, clean = GC.poisoned_case(name), GC.golden_case(name)
+    got = run_seam(case)
+    assert got["renorm"] == 1 and got["num_pos"] == case.num_pos and got["primal_mismatch"] == 0
+    n = int(case.targets["pos_inds"][case.poisoned])
+    nan_fams = {fam for fam in GO.families(case.p) if bool(torch.isnan(GO.flat_family(got["grads"], fam, case.p)[n]).any())}
+    assert nan_fams == {"quat", "ctr", "conf"}
+    check_against_oracle(case, got["grads"], what="poisoned:" + name, nan_row=n)
+    assert run_seam(clean, backward=False)["renorm"] == 0
+
+
+def test_poisoned_quaternion_leaves_the_egocentric_flag_clear(hiplib):
+    """Without PREDICT_ALLOCENTRIC_ROT there is no renormalisation: the same poison (class-agnostic: channel 0) makes its own box NaN
+    and leaves the flags word at 0."""
+    name = "dla34_kitti_variant_egocentric_agnostic"
+    case = GC.poisoned_case(name)
+    got = run_seam(case)
+    assert got["renorm"] == 0 and got["primal_mismatch"] == 0
+    n = int(case.targets["pos_inds"][case.poisoned])
+    assert bool(torch.isnan(GO.flat_family(got["grads"], "quat", case.p)[n]).all())
+    check_against_oracle(case, got["grads"], what="poisoned:" + name, nan_row=n)
 
 
 def test_seam_determinism(hiplib, seam_runs):

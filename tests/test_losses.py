@@ -164,6 +164,25 @@ def test_loss_config_keys_and_loc_loss_type_guard():
         check_loss_config(get_cfg("dd3d_kitti_dla34", {"DD3D": {"FCOS2D": {"LOSS": {"LOC_LOSS_TYPE": "iou"}}}}))
 
 
+def test_focal_gamma_range_guard():
+    """GAMMA == 0 and GAMMA >= 1 are supported; between 0 and 1 the derivative of (1 - p_t)^gamma is infinite at 1 - p_t == 0 (a
+    logit beyond about +-17 in float32) and below 0 the loss itself is, in the reference as well: shown here on torch, and refused."""
+    from dd3d_amd import get_cfg
+    from dd3d_amd.engine.losses import check_loss_config
+    from tests import loss_oracle as LO
+    for gamma in (0.0, 1.0, 1.5, 2.0, 3.0):
+        check_loss_config(get_cfg("dd3d_kitti_dla34", {"DD3D": {"FCOS2D": {"LOSS": {"GAMMA": gamma}}}}))
+        x = torch.tensor([60.0, -60.0, 60.0, -60.0], requires_grad=True)
+        LO.sigmoid_focal_loss(x, torch.tensor([1.0, 0.0, 0.0, 1.0]), 0.25, gamma).backward()
+        assert bool(torch.isfinite(x.grad).all()), gamma
+    for gamma in (0.5, 0.999, -1.0, float("nan")):
+        with pytest.raises(ValueError, match="GAMMA"):
+            check_loss_config(get_cfg("dd3d_kitti_dla34", {"DD3D": {"FCOS2D": {"LOSS": {"GAMMA": gamma}}}}))
+    x = torch.tensor([60.0, -60.0], requires_grad=True)
+    LO.sigmoid_focal_loss(x, torch.tensor([1.0, 0.0]), 0.25, 0.5).backward()
+    assert not bool(torch.isfinite(x.grad).all())  # what the guard keeps out
+
+
 def test_model_still_refuses_train_and_has_the_loss_api():
     import dd3d_amd.modeling  # noqa: F401
     from dd3d_amd import META_ARCH_REGISTRY, get_cfg

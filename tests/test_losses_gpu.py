@@ -283,6 +283,76 @@ def test_compute_losses_full_size(hiplib, exp, weights, B, H, W, ds):
     _close(losses, ref, 5e-6)
 
 
+# ---------------------------------------------------------------------------------------------- away from the released settings
+from tests import loss_grad_cases as GC  # noqa: E402  (imports GOLDEN_CASES from this module)
+
+
+def _forward_close(got, case, what, nan_keys=()):
+    """The project's bar of this seam: every loss within 5e-6 (relative) of the float32 CPU oracle; a key of `nan_keys` is NaN on both
+    sides.  Prints each loss's distance from the float32 and the float64 oracle."""
+    ref, ref64 = case.losses(torch.float32), case.losses(torch.float64)
+    assert list(got) == list(ref), (list(got), list(ref))
+    for k in ref:
+        g, r, r64 = float(got[k]), float(ref[k]), float(ref64[k])
+        print(f"[losses] {what} {k}: kernel {g:.9g} oracle32 {r:.9g} rel {abs(g - r) / max(abs(r), 1e-30):.2e}; against float64 {abs(g - r64) / max(abs(r64), 1e-30):.2e}"
+              f" (oracle32 against float64 {abs(r - r64) / max(abs(r64), 1e-30):.2e})")
+    for k in ref:
+        g, r = float(got[k]), float(ref[k])
+        if k in nan_keys:
+            assert np.isnan(g) and np.isnan(r), (what, k, g, r)
+    _close({k: v for k, v in got.items() if k not in nan_keys}, {k: v for k, v in ref.items() if k not in nan_keys}, 5e-6)
+
+
+def _assert_seam_targets(t, case):
+    """Labels, box2d_reg and the centerness targets of the assignment kernel bit for bit, as in
+    test_loss_kernels_at_seam_on_reference_head_maps."""
+    ref_t = case.targets
+    assert torch.equal(t.labels.cpu().long(), ref_t["labels"]) and torch.equal(t.box2d_reg.cpu(), ref_t["box2d_reg_targets"])
+    assert torch.equal(t.ctr.cpu(), _ctr_ieee(ref_t))
+    assert torch.allclose(t.ctr.cpu(), ref_t["ctr"], rtol=2.0**-23, atol=0.0)
+
+
+@pytest.mark.parametrize("name,key", GC.SETTINGS_ROWS)
+def test_loss_kernels_at_seam_away_from_the_released_settings(hiplib, name, key):
+    """Every row of loss_grad_cases.SETTINGS: the focal loss's powf branch and its alpha switch, plain L1, another temperature and
+    other weights in the loss kernel; CENTER_SAMPLE off and other radii in the assignment kernel, whose targets are compared bit for bit."""
+    case = GC.settings_case(name, key)
+    got, t = _seam(case.model, case.maps, case.inv_K, case.gt, case.level_hw)
+    _assert_seam_targets(t, case)
+    assert case.num_pos > 20 and int(t.flags.cpu()) == 0
+    if key == "no_center_sample" and "nusc" in name:  # the first-box quirk belongs to centre sampling: without it the quirk image has positives
+        B = len(case.gt)
+        assert int(((case.targets["im_inds"] == B - 1) & (case.targets["labels"] != case.model.num_classes)).sum()) > 0
+        assert int(((GC.golden_case(name).targets["im_inds"] == B - 1) & (GC.golden_case(name).targets["labels"] != case.model.num_classes)).sum()) == 0
+    _forward_close(got, case, f"{name}:{key}")
+
+
+@pytest.mark.parametrize("gamma", GC.SATURATED_GAMMAS)
+@pytest.mark.parametrize("H,W", [(4, 4), (1, 257)])
+def test_loss_kernels_on_saturated_logits(hiplib, H, W, gamma):
+    """Logits of +-60 on positives and whole background rows of -60: 1 - p_t is exactly 0 or 1 in float32."""
+    case = GC.handmade_case(H, W, gamma=gamma)
+    got, t = _seam(case.model, case.maps, case.inv_K, case.gt, case.level_hw)
+    _assert_seam_targets(t, case)
+    assert all(np.isfinite(float(v)) for v in got.values())
+    _forward_close(got, case, f"saturated{H}x{W}:gamma{gamma}")
+
+
+@pytest.mark.parametrize("name", GC.POISONED_CASES)
+def test_loss_kernels_on_the_renormalised_path(hiplib, name):
+    """One positive with an all-zero quaternion (loss_grad_cases.poisoned_case) decodes to NaN and sets the batch-wide trigger; every
+    other positive goes through the renormalised branch of decoded_quat.  The families the oracle makes NaN are NaN, the others meet
+    the bar; the flag is 1 here and 0 on the clean case.  (What this does and does not prove: test_loss_grads_gpu.py.)"""
+    case, clean = GC.poisoned_case(name), GC.golden_case(name)
+    got, t = _seam(case.model, case.maps, case.inv_K, case.gt, case.level_hw)
+    assert int(t.flags.cpu()) == 1
+    nan = {k for k, v in case.losses(torch.float64).items() if bool(torch.isnan(v))}
+    assert nan == {"loss_conf3d", "loss_box3d_quat"}
+    _forward_close(got, case, "poisoned:" + name, nan_keys=nan)
+    _, t0 = _seam(clean.model, clean.maps, clean.inv_K, clean.gt, clean.level_hw)
+    assert int(t0.flags.cpu()) == 0
+
+
 # ---------------------------------------------------------------------------------------------- against the reference's own modules
 from tests import test_losses_golden as TG  # noqa: E402
 
