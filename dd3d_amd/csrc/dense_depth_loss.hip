@@ -1,4 +1,4 @@
-// Dense-depth training loss of DD3DDenseDepth for gfx950, without gradients (dense_depth.py:165-171, dense_depth_loss.py:28-36): per pyramid
+// Dense-depth training loss of DD3DDenseDepth for gfx950 (dense_depth.py:165-171, dense_depth_loss.py:28-36; the gradient: dense_depth_loss_grads.hip): per pyramid
 // level the smooth-L1 mean, over the valid ground-truth pixels, between the ground truth and the level's depth map up-sampled to the
 // input resolution -- WITHOUT materialising the up-sampled maps.
 //
@@ -13,6 +13,7 @@
 
 #include "aligned_bilinear.h"
 #include "common.h"
+#include "dense_depth_args.h"
 #include "smooth_l1.h"
 
 DD3D_NOTE_BUILD_FLAGS
@@ -135,21 +136,8 @@ __global__ __launch_bounds__(DT) void dense_depth_finalize_kernel(const DenseDep
 
 extern "C" int dd3d_dense_depth_loss(const dd3d_dense_depth_loss_args* a, void* stream) {
   using namespace dd3d;
-  DD3D_REQUIRE(a != nullptr, "dd3d_dense_depth_loss: null args");
-  DD3D_REQUIRE(a->num_levels >= 1 && a->num_levels <= DD3D_MAX_LEVELS, "dd3d_dense_depth_loss: num_levels = %d outside [1, %d]", a->num_levels,
-               DD3D_MAX_LEVELS);
-  DD3D_REQUIRE(a->gt && a->partials && a->out && a->count, "dd3d_dense_depth_loss: null buffer");
-  DD3D_REQUIRE(a->B >= 1 && a->Hp >= 1 && a->Wp >= 4 && (a->Wp % 4) == 0 && a->pitch >= 1, "dd3d_dense_depth_loss: B = %d, Hp = %d, Wp = %d (a multiple of 4), pitch = %d",
-               a->B, a->Hp, a->Wp, a->pitch);
-  DD3D_REQUIRE(a->Hp < (1 << 23) && a->Wp < (1 << 23), "dd3d_dense_depth_loss: canvas %d x %d: a side must stay below 2^23 (f32 source coordinates)", a->Hp, a->Wp);
-  DD3D_REQUIRE((reinterpret_cast<uintptr_t>(a->gt) & 15) == 0, "dd3d_dense_depth_loss: the ground-truth canvas must be 16-byte aligned");
-  DD3D_REQUIRE(a->focal_factor <= 0.f || a->inv_K, "dd3d_dense_depth_loss: focal scaling needs inv_K");
-  for (int l = 0; l < a->num_levels; ++l) {
-    DD3D_REQUIRE(a->raw[l] != nullptr, "dd3d_dense_depth_loss: level %d has no map", l);
-    DD3D_REQUIRE(a->h[l] >= 1 && a->w[l] >= 1 && a->stride[l] >= 1 && (long)a->h[l] * a->stride[l] == a->Hp && (long)a->w[l] * a->stride[l] == a->Wp,
-                 "dd3d_dense_depth_loss: level %d (%d x %d, stride %d) does not tile the %d x %d canvas", l, a->h[l], a->w[l], a->stride[l], a->Hp,
-                 a->Wp);
-  }
+  const int ok = check_dense_depth_args(a, "dd3d_dense_depth_loss");
+  if (ok != DD3D_OK) return ok;
   const long nquads = (long)a->B * a->Hp * (a->Wp / 4);
   const int grid = (int)((nquads + DT - 1) / DT < DDL_MAX_GRID ? (nquads + DT - 1) / DT : DDL_MAX_GRID);
   DD3D_REQUIRE(a->n_partials >= grid, "dd3d_dense_depth_loss: partials hold %d rows, the launch has %d blocks", a->n_partials, grid);

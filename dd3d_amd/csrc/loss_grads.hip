@@ -39,14 +39,6 @@ __device__ __forceinline__ Box3dDecoded<Du> decode_box3d_seeded(const float* p, 
   return decode_box3d(in, lx, ly, K, cs, a);
 }
 
-// d smooth_l1(x, y, beta) / dx (tridet's, loss_common.h): x - y below beta, sign above it, sign everywhere for beta < 1e-5
-__device__ __forceinline__ float smooth_l1_grad(float x, float y, float beta) {
-  const float r = x - y;
-  const float sg = (float)((r > 0.f) - (r < 0.f));
-  if (beta < 1e-5f) return sg;
-  return fabsf(r) < beta ? r : sg;
-}
-
 // ------------------------------------------------------------------------------------------------ denominators
 __global__ __launch_bounds__(LT) void loss_grad_denoms_kernel(const LossK P, float* denoms, int nblocks) {
   const dd3d_loss_args& a = P.a;

@@ -1,8 +1,10 @@
-"""Dense-depth loss engine: the per-level training loss dict of DD3DDenseDepth on the MI355X, without gradients.
+"""Dense-depth loss engine: the per-level training loss dict of DD3DDenseDepth on the MI355X and, on request, its gradient with respect to
+the head's per-level maps (backward through the convolutions is not implemented).
 
 ``DenseDepthLossPlan`` has the trunk, tower and predictors of ``DenseDepthPlan`` and, in place of the five up-sampling launches, ONE call of
 csrc/dense_depth_loss.hip: a single pass over the ground-truth canvas that evaluates every level's up-sampled prediction in place at the
-valid pixels (dense_depth.py:153-171, dense_depth_loss.py:28-36).  The five full-resolution maps are never allocated.
+valid pixels (dense_depth.py:153-171, dense_depth_loss.py:28-36).  The five full-resolution maps are never allocated.  With
+``head_grads=True`` one more call follows, csrc/dense_depth_loss_grads.hip: the transposed interpolation without float atomics.
 """
 import ctypes as C
 
@@ -40,6 +42,16 @@ def level_divisors(num_levels):
     return [float(np.float32(np.sqrt(2)**l)) for l in range(num_levels)]
 
 
+def dense_depth_grad_args(loss_args, d_raw, upstream, slab):
+    """A DenseDepthGradArgs over per-level NHWC gradient buffers (the layout of the raw maps), the upstream vector and the slab."""
+    g = hip.DenseDepthGradArgs()
+    for l, t in enumerate(d_raw):
+        g.d_raw[l] = t.data_ptr()
+    g.upstream, g.slab, g.n_slab = upstream.data_ptr(), slab.data_ptr(), slab.shape[0]
+    assert len(d_raw) == loss_args.num_levels and slab.shape[1] == hip.DDG_ROW
+    return g
+
+
 def check_depth_maps(depths, image_sizes):
     """Every ground-truth map must be a floating tensor (CPU or device, any float dtype) of shape (Hi, Wi) == its image's own size;
     anything else raises a ValueError that names the image."""
@@ -72,8 +84,9 @@ def stage_depth_canvas(canvas, depths, image_sizes, checked=False):
 
 class DenseDepthLossPlan(DenseDepthPlan):
     """Trunk, box3d tower and per-level predictors of DenseDepthPlan, then one dd3d_dense_depth_loss call on the raw predictor maps and the
-    ground-truth canvas; captured as one hipGraph by DD3DDenseDepth.get_loss_plan."""
-    def __init__(self, model, B, Hp, Wp, device=None, dry_run=False):
+    ground-truth canvas; captured as one hipGraph by DD3DDenseDepth.get_loss_plan.  `head_grads`: one dd3d_dense_depth_loss_backward call
+    more, in the same graph, into gradient buffers the plan owns (upstream = 1: the gradient of the sum of the dict's values)."""
+    def __init__(self, model, B, Hp, Wp, device=None, dry_run=False, head_grads=False):
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
         weight, beta, min_depth, max_depth = dense_depth_loss_config(model.cfg)  # (read here, not in the model's constructor)
         self.adopt_weight_store(model)
@@ -108,6 +121,26 @@ class DenseDepthLossPlan(DenseDepthPlan):
         self.loss_args = a
         self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_dense_depth_loss(C.byref(a), st), "dense_depth_loss"), "dense_depth_loss",
                                dict(kind="dense_depth_loss")))
+        self.grads = bool(head_grads)
+        if self.grads:
+            self._loss_grads(a)
+
+    def _loss_grads(self, a):
+        """Gradient buffers shaped like the raw maps (zeros: the kernel writes channel 0 only), the upstream vector and the slab."""
+        self.d_raw = [torch.zeros_like(m.t) for m in self.dd_raw]
+        self.upstream = torch.ones(a.num_levels, dtype=torch.float32, device=self.device)
+        self.grad_slab = torch.zeros((hip.dense_depth_grad_rows(a), hip.DDG_ROW), dtype=torch.float32, device=self.device)
+        g = dense_depth_grad_args(a, self.d_raw, self.upstream, self.grad_slab)
+        self.grad_args = g
+        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_dense_depth_loss_backward(C.byref(a), C.byref(g), st), "dense_depth_loss_backward"),
+                               "dense_depth_loss_backward", dict(kind="dense_depth_loss_backward")))
+
+    def head_grads(self):
+        """The gradients of the last run: {"dense_depth<l>": (B, 1, h_l, w_l) float32} (copies), with respect to the head's per-level
+        outputs after Scale and Offset."""
+        if not self.grads:
+            raise RuntimeError("this DenseDepthLossPlan was built without head_grads=True")
+        return {f"dense_depth{l}": d[..., 0].unsqueeze(1).clone() for l, d in enumerate(self.d_raw)}
 
     def stage_depth(self, depths, image_sizes, checked=False):
         """The batch's ground-truth maps into the device canvas, on the current stream (ahead of the run that reads it)."""

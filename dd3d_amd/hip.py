@@ -202,13 +202,31 @@ class DenseDepthLossArgs(C.Structure):
     ]
 
 
+DDG_ROW = 4  # floats per slab row of dd3d_dense_depth_loss_backward: the four corner sums of one sub-tile of a cell
+
+
+class DenseDepthGradArgs(C.Structure):
+    """`dd3d_dense_depth_grad_args`."""
+    _fields_ = [("d_raw", C.c_void_p * MAX_LEVELS), ("upstream", C.c_void_p), ("slab", C.c_void_p), ("n_slab", C.c_int64)]
+
+
+def dense_depth_grad_rows(args):
+    """Slab rows one dd3d_dense_depth_loss_backward call on the filled-in DenseDepthLossArgs `args` writes (the library's own count: one
+    row per level, image, cell and sub-tile); raises like `check` when the gradient cannot run on these args."""
+    n = lib().dd3d_dense_depth_grad_rows(C.byref(args))
+    if n < 0:
+        raise RuntimeError(f"libdd3d_hip dense_depth_grad_rows failed: {lib().dd3d_last_error().decode()}")
+    return int(n)
+
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
     "dd3d_invert_intrinsics", "dd3d_nms_finalize", "dd3d_bev_nms_aggregate", "dd3d_conv2d_smallc_supported", "dd3d_conv2d_smallc_bf16x3", "dd3d_rotate_iou_eval", "dd3d_d3_box_overlap", "dd3d_image_box_overlap", "dd3d_aligned_bilinear_scale", "dd3d_resize_bilinear_u8",
     "dd3d_format_boxes3d", "dd3d_math_planes", "dd3d_split_planes", "dd3d_maxpool2x2_planes", "dd3d_maxpool2x2_planes_in", "dd3d_upsample2x_add_planes", "dd3d_ese_fused", "dd3d_stem_fused_f16x2", "dd3d_fold_range_flags", "dd3d_pack_readback",
     "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match", "dd3d_loss_assign", "dd3d_loss_terms", "dd3d_loss_layout",
-    "dd3d_dense_depth_loss", "dd3d_dense_depth_loss_layout", "dd3d_loss_backward", "dd3d_loss_grad_layout"
+    "dd3d_dense_depth_loss", "dd3d_dense_depth_loss_layout", "dd3d_loss_backward", "dd3d_loss_grad_layout",
+    "dd3d_dense_depth_loss_backward", "dd3d_dense_depth_grad_rows", "dd3d_dense_depth_grad_layout"
 ]
 
 
@@ -283,6 +301,10 @@ def lib():
     L.dd3d_loss_grad_layout.argtypes = [C.c_void_p, C.c_int32]
     L.dd3d_dense_depth_loss.argtypes = [C.POINTER(DenseDepthLossArgs), C.c_void_p]
     L.dd3d_dense_depth_loss_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_dense_depth_loss_backward.argtypes = [C.POINTER(DenseDepthLossArgs), C.POINTER(DenseDepthGradArgs), C.c_void_p]
+    L.dd3d_dense_depth_grad_rows.argtypes = [C.POINTER(DenseDepthLossArgs)]
+    L.dd3d_dense_depth_grad_rows.restype = C.c_int64
+    L.dd3d_dense_depth_grad_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

@@ -6,6 +6,10 @@ csrc/loss_grads.hip).  ``head_maps`` holds the reference's per-level NCHW head o
 (post-ReLU), ``centerness<l>``, ``quat<l>``, ``ctr<l>``, ``depth<l>``, ``size<l>``, ``conf<l>`` and, for NuscenesDD3D, ``attr<l>`` and
 ``speed<l>``; they may require grad and may be the outputs of further torch ops.  The result is the reference's loss dict, keys in its
 order, as 0-d tensors that carry the gradient.  No double backward.
+
+``FusedDenseDepthLoss(model)(dense_depth_maps, intrinsics, depths)`` does the same for the depth pre-training network: it replaces the
+aligned_bilinear up-sampling, the focal-length division and DenseDepthL1Loss of the reference's DD3DDenseDepth.forward by one fused
+launch in forward and one in backward (csrc/dense_depth_loss.hip, csrc/dense_depth_loss_grads.hip); the up-sampled maps are never stored.
 """
 import ctypes as C
 
@@ -155,3 +159,114 @@ class FusedDD3DLoss:
         out = _FusedLossFn.apply(st, *[head_maps[f"{k}{l}"] for l in range(len(level_hw)) for k in fams])
         keys = E.loss_keys(not model.only_box2d, E.model_is_nusc(model), st.num_pos)
         return {k: out[E.OUT_INDEX[k]] for k in keys}
+
+
+def check_dense_depth_maps(model, dense_depth_maps, device_type="cuda"):
+    """Level count, device, dtype and shapes of the per-level (B, 1, h, w) maps against the model's strides; returns (B, Hp, Wp).
+    `device_type`: where the maps must live (the kernels run on the HIP device only; the tests check the other rules on CPU tensors)."""
+    strides = [int(s.stride) for s in model.backbone_output_shape]
+    if not isinstance(dense_depth_maps, (list, tuple)):
+        raise ValueError("dense_depth_maps must be the per-level list of (B, 1, h, w) tensors")
+    if len(dense_depth_maps) != len(strides):
+        raise ValueError(f"dense_depth_maps has {len(dense_depth_maps)} levels; the model has {len(strides)} (strides {strides})")
+    B = Hp = Wp = None
+    for l, (t, s) in enumerate(zip(dense_depth_maps, strides)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[1] != 1:
+            raise ValueError(f"dense_depth_maps[{l}] must be a (B, 1, h, w) tensor" + (f", got shape {tuple(t.shape)}" if isinstance(t, torch.Tensor) else ""))
+        if t.device.type != device_type:
+            raise ValueError(f"dense_depth_maps[{l}] is on {t.device}: the fused loss runs on the HIP device only")
+        if t.dtype != torch.float32:
+            raise ValueError(f"dense_depth_maps[{l}] is {t.dtype}; float32 expected")
+        if B is None:
+            B, Hp, Wp = int(t.shape[0]), int(t.shape[2]) * s, int(t.shape[3]) * s
+            if Wp % 4:
+                raise ValueError(f"dense_depth_maps[0] gives a canvas {Wp} wide; the width must be a multiple of 4")
+        if int(t.shape[0]) != B or int(t.shape[2]) * s != Hp or int(t.shape[3]) * s != Wp:
+            raise ValueError(f"dense_depth_maps[{l}] has shape {tuple(t.shape)} at stride {s}: it does not tile the {B} x {Hp} x {Wp} canvas of level 0")
+    return B, Hp, Wp
+
+
+class _FusedDenseDepthLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, st, *maps):
+        from dd3d_amd.engine import dense_depth_loss as D
+        model, B, Hp, Wp = st.model, st.B, st.Hp, st.Wp
+        dev, L = maps[0].device, len(maps)
+        weight, beta, min_depth, max_depth = D.dense_depth_loss_config(model.cfg)
+        lib = hip.lib()
+        raw = [m.detach().contiguous() for m in maps]  # (B, 1, h, w) contiguous IS the kernel's NHWC layout at pitch 1
+        a = hip.DenseDepthLossArgs()
+        for l, (r, s) in enumerate(zip(raw, model.backbone_output_shape)):
+            a.raw[l], a.h[l], a.w[l], a.stride[l] = r.data_ptr(), int(r.shape[2]), int(r.shape[3]), int(s.stride)
+        for l, d in enumerate(D.level_divisors(L)):
+            a.divisor[l] = d
+        canvas = D.stage_depth_canvas(torch.empty((B, Hp, Wp), dtype=torch.float32, device=dev), st.depths, [tuple(d.shape) for d in st.depths], checked=True)
+        keep = raw + [canvas]
+        if model.scale_depth_by_focal_lengths:
+            K = st.intrinsics.detach().to(dev, torch.float32).reshape(B, 9).contiguous()
+            inv_K = torch.empty_like(K)
+            hip.check(lib.dd3d_invert_intrinsics(K.data_ptr(), inv_K.data_ptr(), B, hip.current_stream()), "invert_intrinsics")
+            a.inv_K, a.focal_factor = inv_K.data_ptr(), float(model.scale_depth_by_focal_lengths_factor)
+            keep += [K, inv_K]
+        nb = hip.dense_depth_loss_blocks(B, Hp, Wp)
+        partials = torch.empty((nb, hip.DDL_ROW), dtype=torch.float32, device=dev)
+        out = torch.empty(L, dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        a.gt, a.partials, a.n_partials, a.out, a.count = canvas.data_ptr(), partials.data_ptr(), nb, out.data_ptr(), count.data_ptr()
+        a.num_levels, a.B, a.Hp, a.Wp, a.pitch = L, B, Hp, Wp, 1
+        a.offset_half = int(model.feature_locations_offset == "half")
+        a.min_depth, a.max_depth, a.beta, a.loss_weight = min_depth, max_depth, beta, weight
+        st.grad_rows = hip.dense_depth_grad_rows(a)  # (host only: a geometry the gradient cannot take raises here, before the launch)
+        hip.check(lib.dd3d_dense_depth_loss(C.byref(a), hip.current_stream()), "dense_depth_loss")
+        st.args, st.keep = a, keep + [partials, out, count]
+        ctx.st = st
+        return out.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        from dd3d_amd.engine.dense_depth_loss import dense_depth_grad_args
+        st = ctx.st
+        a, dev = st.args, grad_out.device
+        up = grad_out.detach().to(torch.float32).contiguous()
+        # channel 0 of every pixel is written by the kernel, and at pitch 1 there is no other
+        d_raw = [torch.empty_like(r) for r in st.keep[:a.num_levels]]
+        slab = torch.empty((st.grad_rows, hip.DDG_ROW), dtype=torch.float32, device=dev)
+        g = dense_depth_grad_args(a, d_raw, up, slab)
+        hip.check(hip.lib().dd3d_dense_depth_loss_backward(C.byref(a), C.byref(g), hip.current_stream()), "dense_depth_loss_backward")
+        return (None, ) + tuple(d_raw)
+
+
+class FusedDenseDepthLoss:
+    """`model`: a dd3d_amd DD3DDenseDepth (its config gives the loss settings, the strides, the location offset and the focal scaling; its
+    weights are not used).  Call with the head's per-level (B, 1, h, w) float32 maps (the reference's `dense_depth_lvl` list, after Scale
+    and Offset), the images' intrinsics (B, 3, 3) -- None when SCALE_DEPTH_BY_FOCAL_LENGTHS is off -- and the per-image ground-truth depth
+    maps (Hi, Wi), 0 = no return.  Returns the reference's dict `loss_dense_depth_lvl_<l>` of 0-d tensors that carry the gradient."""
+    def __init__(self, model):
+        from dd3d_amd.engine.dense_depth_loss import dense_depth_loss_config
+        dense_depth_loss_config(model.cfg)
+        self.model = model
+
+    def __call__(self, dense_depth_maps, intrinsics, depths):
+        from dd3d_amd.engine.dense_depth_loss import check_depth_maps
+        model = self.model
+        B, Hp, Wp = check_dense_depth_maps(model, dense_depth_maps)
+        if model.scale_depth_by_focal_lengths:
+            if intrinsics is None:
+                raise ValueError("intrinsics is None: SCALE_DEPTH_BY_FOCAL_LENGTHS needs the (B, 3, 3) intrinsics")
+            intrinsics = torch.as_tensor(intrinsics)
+            if tuple(intrinsics.shape) != (B, 3, 3):
+                raise ValueError(f"intrinsics has shape {tuple(intrinsics.shape)} for {B} images; expected ({B}, 3, 3)")
+        depths = list(depths)
+        if len(depths) != B:
+            raise ValueError(f"{len(depths)} depth maps for dense_depth_maps of {B} images")
+        for i, d in enumerate(depths):
+            if not isinstance(d, torch.Tensor) or d.dim() != 2:
+                raise ValueError(f"image {i}: 'depth' must be an (Hi, Wi) floating-point tensor")
+            if d.shape[0] > Hp or d.shape[1] > Wp:
+                raise ValueError(f"image {i}: its depth map {tuple(d.shape)} does not fit the {Hp} x {Wp} canvas of the maps")
+        check_depth_maps(depths, [tuple(d.shape) for d in depths])
+        st = _State()
+        st.model, st.B, st.Hp, st.Wp, st.intrinsics, st.depths = model, B, Hp, Wp, intrinsics, depths
+        out = _FusedDenseDepthLossFn.apply(st, *dense_depth_maps)
+        return {f"loss_dense_depth_lvl_{l}": out[l] for l in range(len(dense_depth_maps))}

@@ -5,7 +5,8 @@ bilinear upsampling of every level to the input resolution and the focal-length 
 The reference's ``forward`` only defines the training branch (it ends in ``raise NotImplementedError()`` in eval mode,
 dense_depth.py:162-163); everything it computes before the losses is inference math, exposed here as
 ``predict_dense_depth(batched_inputs)``; ``forward`` keeps the reference's eval-mode behaviour.  What the training branch adds, the
-per-level loss dict (dense_depth.py:165-171), is ``compute_losses(batched_inputs)``: values only, no gradients.
+per-level loss dict (dense_depth.py:165-171), is ``compute_losses(batched_inputs)``; with ``head_grads=True`` also the gradient with
+respect to the head's per-level maps (no backward through the convolutions).
 """
 import torch
 from torch import nn
@@ -153,19 +154,24 @@ class DD3DDenseDepth(nn.Module):
         plan.check_status()  # one 4-byte read behind the forward (the caller is about to consume the maps anyway); raises and clears
         return [m for m in plan.depth_maps]
 
-    def get_loss_plan(self, B, Hp, Wp):
+    def get_loss_plan(self, B, Hp, Wp, head_grads=False):
         """The loss plan (engine.DenseDepthLossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the
-        prediction plans, under a key of its own."""
+        prediction plans, under a key of its own (another one with `head_grads`: the backward call is part of that plan's graph)."""
         from dd3d_amd.engine import DenseDepthLossPlan
+        if head_grads:
+            return self._cached_plan(("dense_depth_loss_grads", B, Hp, Wp, self.math), lambda: DenseDepthLossPlan(self, B, Hp, Wp, head_grads=True))
         return self._cached_plan(("dense_depth_loss", B, Hp, Wp, self.math), lambda: DenseDepthLossPlan(self, B, Hp, Wp))
 
     @torch.no_grad()
-    def compute_losses(self, batched_inputs):
+    def compute_losses(self, batched_inputs, head_grads=False):
         """The loss dict of the reference's training forward (dense_depth.py:165-171) for a labelled batch: each item carries `image`,
         `intrinsics` and `depth`, an (Hi, Wi) float map of the image's own size (0 = no return).  Keys `loss_dense_depth_lvl_{l}` in
         level order, values 0-d float32 tensors on the model's device; NaN at every level when no pixel of the batch is valid.  Needs
         DD3D.FCOS3D.DEPTH_HEAD.{LOSS_TYPE, LOSS_WEIGHT} in the config (ValueError otherwise).  Every norm layer uses its running
-        statistics; no gradients.  The f16x2 range guard acts as in predict_dense_depth."""
+        statistics.  The f16x2 range guard acts as in predict_dense_depth.  With `head_grads` the result is (loss dict, grads): the
+        gradient of the sum of the dict's values with respect to the head's per-level outputs (the reference's `dense_depth_lvl`, after
+        Scale and Offset), {"dense_depth<l>": (B, 1, h_l, w_l) float32 device tensor}; all zeros when no pixel is valid.  There is no
+        backward through the convolutions."""
         from dd3d_amd.engine import relax_arithmetic
         for i, x in enumerate(batched_inputs):
             if "depth" not in x:
@@ -175,17 +181,18 @@ class DD3DDenseDepth(nn.Module):
         check_depth_maps([x["depth"] for x in batched_inputs], [(int(x["image"].shape[-2]), int(x["image"].shape[-1])) for x in batched_inputs])
         while True:
             try:
-                return self._compute_losses(batched_inputs)
+                return self._compute_losses(batched_inputs, head_grads)
             except FloatingPointError as e:
                 if not relax_arithmetic(self, e):
                     raise
 
-    def _compute_losses(self, batched_inputs):
-        plan, sizes = self._stage(batched_inputs, self.get_loss_plan)
+    def _compute_losses(self, batched_inputs, head_grads=False):
+        get_plan = (lambda B, H, W: self.get_loss_plan(B, H, W, head_grads=True)) if head_grads else self.get_loss_plan
+        plan, sizes = self._stage(batched_inputs, get_plan)
         plan.stage_depth([x["depth"] for x in batched_inputs], sizes, checked=True)  # (compute_losses has validated the maps)
         plan.run()
         plan.check_status()
-        return plan.loss_dict()
+        return (plan.loss_dict(), plan.head_grads()) if head_grads else plan.loss_dict()
 
     def forward(self, batched_inputs):
         raise NotImplementedError()  # the reference's eval-mode forward (dense_depth.py:162-163)

@@ -1,7 +1,7 @@
 /*
  * dd3d_hip.h -- C ABI of the MI355X (gfx950) DD3D forward-path library  (libdd3d_hip.so): the forward, the evaluators' kernels and the
  * training losses (detector: dd3d_loss_*, with the head-map gradients of dd3d_loss_backward; depth pre-training: dd3d_dense_depth_loss,
- * values only)
+ * with the gradient at the head's per-level maps of dd3d_dense_depth_loss_backward)
  *
  * The reference (TRI-ML/dd3d) has no FFI of its own for this path: it is pure Python and reaches
  * native code only through third-party wheels (cuDNN via torch, torchvision.ops.nms,
@@ -697,7 +697,7 @@ int dd3d_loss_backward(const dd3d_loss_args* args, const dd3d_loss_grad_args* gr
 int dd3d_loss_grad_layout(int64_t* out, int32_t n);
 
 /* ------------------------------------------------------------------------------------------------
- * Dense-depth training loss of DD3DDenseDepth without gradients (csrc/dense_depth_loss.hip).
+ * Dense-depth training loss of DD3DDenseDepth (csrc/dense_depth_loss.hip); its gradient follows below.
  * Replaces the training branch of DD3DDenseDepth.forward after the head (tridet/modeling/dd3d/dense_depth.py:153-171: aligned_bilinear
  * of every level, the focal-length scaling, DenseDepthL1Loss per level and the / sqrt(2)^level) and DenseDepthL1Loss.forward
  * (dense_depth_loss.py:28-36) with tridet/layers/smooth_l1_loss.py.
@@ -733,6 +733,43 @@ typedef struct dd3d_dense_depth_loss_args {  /* host memory */
 } dd3d_dense_depth_loss_args;
 int dd3d_dense_depth_loss(const dd3d_dense_depth_loss_args* args, void* stream);
 int dd3d_dense_depth_loss_layout(int64_t* out, int32_t n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gradient of the dense-depth loss above with respect to the raw per-level maps (csrc/dense_depth_loss_grads.hip):
+ *   d_raw[l] = d (sum_l upstream[l] * out[l]) / d raw[l]
+ * the derivative torch autograd gives DenseDepthL1Loss behind aligned_bilinear and the focal-length division.  With N = count[0],
+ *   d_raw[l](b, i, j) = upstream[l] * loss_weight / (divisor[l] * N * pix_b)
+ *                       * sum over the valid pixels p of image b whose taps include (i, j) of tapweight(p; i, j) * s'(pred_l(p) - gt(p))
+ * pix_b = |(invK00, invK11)| * focal_factor (1 without focal scaling); s'(d) = d for |d| < beta, sign(d) otherwise and everywhere for
+ * beta < 1e-5, sign(0) = 0.  N == 0: every gradient is 0 (the losses are NaN).  A NaN ground-truth pixel counts in N and adds 0 (its
+ * difference compares false both ways); a NaN or infinite prediction makes the four taps of its cell NaN at that level, nothing else.
+ *
+ * dd3d_dense_depth_loss_backward runs after dd3d_dense_depth_loss on the same `args` and stream and reads the count[0] that call wrote;
+ *   nothing is read back to the host.  The transposed interpolation is a scatter; it is done without float atomics in two launches:
+ *   (1) the pixels that share their four taps at a level (a "cell": stride x stride pixels, shifted by stride / 2 under offset_half,
+ *   the border cells larger or smaller) are cut into sub-tiles of at most ~1024 pixels; one wave per sub-tile sums
+ *   tapweight * s' for the four corners in a fixed order into one slab row; (2) one thread per raw pixel adds the rows of the up to
+ *   four cells around it (up to nine corner sums at the replicated last row / column) in a fixed order, scales and stores.  No
+ *   full-resolution map is stored; two runs agree bit for bit.
+ * d_raw[l]: NHWC f32 with the pitch of raw[l]; channel 0 of EVERY raw pixel is written (zeros included: no memset is needed), the
+ *   other channels are untouched.
+ * slab: >= dd3d_dense_depth_grad_rows(args) rows of DD3D_DDG_ROW floats, 16-byte aligned; n_slab says how many there are.
+ * Beyond the forward's conditions every stride must be a multiple of 4 (of 8 under offset_half: a 16-byte load never straddles two
+ *   cells) and such that the f32 source coordinates of one cell's pixels truncate to one index (every power of two does); the call is
+ *   rejected otherwise, before anything is launched.
+ * dd3d_dense_depth_grad_rows: the slab rows one backward call on `args` writes (host only; -1 and dd3d_last_error on bad args).
+ * dd3d_dense_depth_grad_layout: sizeof(dd3d_dense_depth_grad_args) and the byte offsets of its fields (layout check of the bindings).
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_DDG_ROW 4
+typedef struct dd3d_dense_depth_grad_args {  /* host memory */
+  float* d_raw[DD3D_MAX_LEVELS];      /* per level: [B][h][w][pitch], the layout of dd3d_dense_depth_loss_args.raw (device) */
+  const float* upstream;              /* device, num_levels floats: d total / d out[l] */
+  float* slab;                        /* device scratch, [n_slab][DD3D_DDG_ROW] */
+  int64_t n_slab;
+} dd3d_dense_depth_grad_args;
+int dd3d_dense_depth_loss_backward(const dd3d_dense_depth_loss_args* args, const dd3d_dense_depth_grad_args* grads, void* stream);
+int64_t dd3d_dense_depth_grad_rows(const dd3d_dense_depth_loss_args* args);
+int dd3d_dense_depth_grad_layout(int64_t* out, int32_t n);
 
 #ifdef __cplusplus
 }
