@@ -156,6 +156,7 @@ class ForwardPlan(PlanBase, BackboneLowering):
         C_ = model.num_classes
 
         pred_groups = []  # every predictor group becomes a set of segments of ONE launch (see the end of this method)
+        self.pred_info = {}  # group name -> what the predictor backward (engine.losses) needs: modules, per-level scales, clamp, tower
 
         def fused_predictor(name, convs, tower_idx, level_scale, level_bias_extra, lo):
             """convs: list of (module per level-or-shared) concatenated along N.  level_scale(l) -> per-channel scale vector."""
@@ -183,6 +184,7 @@ class ForwardPlan(PlanBase, BackboneLowering):
                     "lo": None if lo is None else self._vec(lo), "n_limit": n_total
                 })
             pred_groups.append((name, metas, segs))
+            self.pred_info[name] = dict(convs=convs, tower=tower_idx, n=n_total, pitch=pitch, lo=lo, scales=[level_scale(l) for l in range(L)])
             return maps, pitch
 
         ones = lambda n: torch.ones(n)

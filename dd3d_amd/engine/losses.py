@@ -1,5 +1,7 @@
 """Loss engine: target assignment and the training loss dict of DD3D / NuscenesDD3D on the MI355X, and on request the gradient of
-the dict's weighted sum with respect to the head maps (csrc/loss_grads.hip; backward through the convolutions is not implemented).
+the dict's weighted sum with respect to the head maps (csrc/loss_grads.hip) and, one layer further down, with respect to the predictor
+layer's parameters and the tower outputs it reads (csrc/predictor_grads.hip).  The backward stops there: towers, FPN and backbone have
+none, and there is no optimiser, batch-statistics norm or model.train().
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -257,12 +259,76 @@ def unpack_head_grads(d_cls, d_b2d, d_b3d, num_classes, num_attr, class_agnostic
     return out
 
 
+def pred_act_mode(plan):
+    """DD3D_PG_ACT_* of the storage a plan keeps its tower outputs in; the reduced modes have no loader."""
+    if not plan.use_planes:
+        return hip.PG_ACT_F32
+    if plan.math == hip.MATH_F16X2:
+        return hip.PG_ACT_F16X2
+    if plan.math == hip.MATH_BF16X3:
+        return hip.PG_ACT_BF16X3
+    name = {hip.MATH_BF16X2: "bf16x2", hip.MATH_BF16: "bf16"}.get(plan.math, str(plan.math))
+    raise NotImplementedError(f"predictor gradients read f32, f16x2 or bf16x3 tower outputs; the arithmetic mode {name!r} has no loader")
+
+
+class PredGroupGrads:
+    """Buffers and dd3d_pred_grad_args of one predictor group (the predictors fused into one head map, reading one tower).
+
+    `act`: per-level device address of the tower output in the storage `act_mode` names; `g`, `maps`: per-level NHWC tensors of pitch
+    `g_pitch`; `w`: per-level [n, 3, 3, Cin] filters, the SAME tensor on the levels that share a module; `bias`, `scale`: per-level [n];
+    `lo`: [n] or None; `slot`: int32 [n] or None.  Outputs are allocated here, filled with `fill` and followed by `guard` words of it."""
+    def __init__(self, device, B, level_hw, Cin, n, g_pitch, act, act_mode, act_pitch, plane_scale, g, maps, w, bias, scale, lo=None, slot=None,
+                 fill=0.0, guard=0):
+        L = len(level_hw)
+        self.B, self.level_hw, self.Cin, self.n, self.L = B, list(level_hw), Cin, n, L
+        self.keep = (g, maps, w, bias, scale, lo, slot)
+        a = hip.PredGradArgs()
+        self._raw = []
+
+        def out(*shape):
+            numel = int(np.prod(shape))
+            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
+            self._raw.append((t, numel))
+            return t[:numel].view(*shape)
+
+        K9 = 9 * Cin
+        self.n_slices = hip.pred_grad_slices(B, level_hw)
+        self.part, self.qpart = out(self.n_slices, n, K9), out(self.n_slices, n)
+        self.dw_level, self.dw, self.db = out(L, n, K9), out(L, n, K9), out(L, n)
+        self.q, self.r = out(L, n), out(L, n)
+        self.dscale, self.doffset = out(L, hip.PG_MAX_SLOTS), out(L, hip.PG_MAX_SLOTS)
+        self.da = [out(B, h, w_, Cin) for h, w_ in level_hw]
+        for l, (h, w_) in enumerate(level_hw):
+            a.act[l] = act[l] or None
+            a.g[l], a.map[l] = g[l].data_ptr(), (maps[l].data_ptr() if maps is not None else None)
+            a.w[l], a.bias[l], a.scale[l] = w[l].data_ptr(), bias[l].data_ptr(), scale[l].data_ptr()
+            a.da[l] = self.da[l].data_ptr()
+            a.H[l], a.W[l] = int(h), int(w_)
+        a.lo = lo.data_ptr() if lo is not None else None
+        a.slot = slot.data_ptr() if slot is not None else None
+        a.part, a.qpart, a.dw_level, a.dw, a.db = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw, self.db))
+        a.q, a.r, a.dscale, a.doffset = (t.data_ptr() for t in (self.q, self.r, self.dscale, self.doffset))
+        a.num_levels, a.B, a.Cin, a.n, a.g_pitch = L, int(B), int(Cin), int(n), int(g_pitch)
+        a.act_mode, a.act_pitch, a.n_slices, a.plane_scale = int(act_mode), int(act_pitch), self.n_slices, float(plane_scale)
+        self.args = a
+        # the first level of every distinct filter: the rows of dw / db that are written
+        self.owners = [l for l in range(L) if all(w[m].data_ptr() != w[l].data_ptr() for m in range(l))]
+
+    def launch(self, lib, st):
+        hip.check(lib.dd3d_predictor_wgrad(C.byref(self.args), st), "predictor_wgrad")
+        hip.check(lib.dd3d_predictor_dgrad(C.byref(self.args), st), "predictor_dgrad")
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
 class LossPlan(ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
-    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False):
+    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False):
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
-        self.grads = bool(grads)
+        self.pred_grads = bool(pred_grads)
+        self.grads = bool(grads) or self.pred_grads
         check_loss_config(model.cfg)
         from dd3d_amd.engine.tiling import default_tile_policy
         self.tile_policy = default_tile_policy() or getattr(model, "tile_policy", None) or "latency"  # as ForwardPlan: the forward's own tiles
@@ -319,6 +385,8 @@ class LossPlan(ForwardPlan):
                                dict(kind="loss_terms")))
         if self.grads:
             self._loss_grads(a)
+        if self.pred_grads:
+            self._pred_grads(model)
 
     def _loss_grads(self, a):
         """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
@@ -332,6 +400,77 @@ class LossPlan(ForwardPlan):
         self.grad_args = g
         self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_backward(C.byref(a), C.byref(g), st), "loss_backward"), "loss_backward",
                                dict(kind="loss_backward")))
+
+    def _pred_grads(self, model):
+        """The predictor layer's backward behind dd3d_loss_backward, one weight-gradient and one input-gradient call per predictor group
+        (= per tower) on the main stream -- still one hipGraph."""
+        dev, L = self.device, len(self.features)
+        mode = pred_act_mode(self)
+        h2, h3 = model.fcos2d_head, (None if model.only_box2d else model.fcos3d_head)
+        level_hw = [(f.H, f.W) for f in self.features]
+        C3 = (1 if h3.class_agnostic else int(model.num_classes)) if h3 is not None else 0
+        # (first channel, channels, slot, Scale list, Offset list) of the per-level scalars of a group
+        slots = {"cls_map": [], "box2d_map": [(0, 4, 0, h2.scales_box2d_reg, None)] if h2.use_scale else [], "box3d_map": []}
+        if h3 is not None and h3.use_scale:
+            slots["box3d_map"] = [(4 * C3, 2 * C3, 0, h3.scales_proj_ctr, None), (6 * C3, C3, 1, h3.scales_depth, h3.offsets_depth),
+                                  (7 * C3, 3 * C3, 2, h3.scales_size, None), (10 * C3, C3, 3, h3.scales_conf, None)]
+        grads = {"cls_map": self.d_cls, "box2d_map": self.d_b2d, "box3d_map": self.d_b3d}
+        maps = {"cls_map": self.cls_maps, "box2d_map": self.b2d_maps, "box3d_map": self.b3d_maps}
+        self.pred_groups = {}
+        for name, info in self.pred_info.items():
+            n, t = info["n"], info["tower"]
+            ws, w, bias = {}, [], []
+            for l in range(L):
+                mods = [c[l if len(c) > 1 else 0] for c in info["convs"]]
+                key = tuple(id(m) for m in mods)
+                if key not in ws:
+                    wt = torch.cat([m.weight.detach().float() for m in mods]).permute(0, 2, 3, 1).contiguous().to(dev)
+                    bt = torch.cat([m.bias.detach().float() if m.bias is not None else torch.zeros(m.out_channels, device=m.weight.device) for m in mods])
+                    ws[key] = (wt, bt.contiguous().to(dev))
+                w.append(ws[key][0])
+                bias.append(ws[key][1])
+            Cin = int(w[0].shape[-1])
+            slot = torch.full((n, ), -1, dtype=torch.int32)
+            for c0, cn, j, _, _ in slots[name]:
+                slot[c0:c0 + cn] = j
+            tv = [self.tower_out[l][t] for l in range(L)]
+            act = [(v.ptr if mode == hip.PG_ACT_F32 else v.pptr) for v in tv]
+            grp = PredGroupGrads(dev, self.B, level_hw, Cin, n, info["pitch"], act, mode, tv[0].pitch, tv[0].buf.plane_scale,
+                                 grads[name], [m.t for m in maps[name]], w, bias, [self._vec(sc) for sc in info["scales"]],
+                                 lo=None if info["lo"] is None else self._vec(info["lo"]), slot=slot.to(dev))
+            grp.convs, grp.slots, grp.tower = info["convs"], slots[name], ("cls", "box2d", "box3d")[t]
+            self.pred_groups[name] = grp
+            self.ops.append(CallOp(lambda lib, st, grp=grp: grp.launch(lib, st), "predictor_grads." + name,
+                                   dict(kind="predictor_grads", group=name)))
+
+    def predictor_grads(self):
+        """(tower-output gradients, parameter gradients) of the last run, copies: {<tower>_tower_out<l>: (B, Cin, h_l, w_l)} and
+        {name in model.named_parameters(): tensor of the parameter's shape}, float32."""
+        if not self.pred_grads:
+            raise RuntimeError("this LossPlan was built without pred_grads=True")
+        names = {id(p): k for k, p in self.model.named_parameters()}
+        towers, params = {}, {}
+        for grp in self.pred_groups.values():
+            for l in range(grp.L):
+                towers[f"{grp.tower}_tower_out{l}"] = grp.da[l].permute(0, 3, 1, 2).clone()
+            c0 = 0
+            for conv in grp.convs:
+                oc = conv[0].out_channels
+                # a per-level module owns its level's row; a shared one the sum over the rows written (one row when the whole group is shared)
+                for m, rows in (zip(conv, [[l] for l in range(grp.L)]) if len(conv) > 1 else [(conv[0], grp.owners)]):
+                    dw, db = grp.dw[rows[0], c0:c0 + oc].clone(), grp.db[rows[0], c0:c0 + oc].clone()
+                    for l in rows[1:]:
+                        dw, db = dw + grp.dw[l, c0:c0 + oc], db + grp.db[l, c0:c0 + oc]
+                    params[names[id(m.weight)]] = dw.view(oc, 3, 3, grp.Cin).permute(0, 3, 1, 2).contiguous()
+                    if m.bias is not None:
+                        params[names[id(m.bias)]] = db
+                c0 += oc
+            for _, _, j, scales, offsets in grp.slots:
+                for l in range(grp.L):
+                    params[names[id(scales[l].scale)]] = grp.dscale[l, j:j + 1].clone()
+                    if offsets is not None:
+                        params[names[id(offsets[l].bias)]] = grp.doffset[l, j:j + 1].clone()
+        return towers, params
 
     def head_grads(self):
         """The gradients of the last run as NCHW per-level tensors (copies) under the keys of the reference's head maps."""

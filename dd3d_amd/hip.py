@@ -219,6 +219,30 @@ def dense_depth_grad_rows(args):
     return int(n)
 
 
+PG_MAX_SLOTS, PG_MAX_N, PG_UNIT = 8, 256, 64
+PG_ACT_F32, PG_ACT_F16X2, PG_ACT_BF16X3 = 0, 1, 2
+PG_TARGET_SLICES = 48  # csrc/predictor_grads.hip::PG_TARGET_SLICES
+
+
+class PredGradArgs(C.Structure):
+    """`dd3d_pred_grad_args`."""
+    _fields_ = [
+        ("act", C.c_void_p * MAX_LEVELS), ("g", C.c_void_p * MAX_LEVELS), ("map", C.c_void_p * MAX_LEVELS), ("w", C.c_void_p * MAX_LEVELS),
+        ("bias", C.c_void_p * MAX_LEVELS), ("scale", C.c_void_p * MAX_LEVELS), ("da", C.c_void_p * MAX_LEVELS), ("lo", C.c_void_p),
+        ("slot", C.c_void_p), ("part", C.c_void_p), ("qpart", C.c_void_p), ("dw_level", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p),
+        ("q", C.c_void_p), ("r", C.c_void_p), ("dscale", C.c_void_p), ("doffset", C.c_void_p), ("H", C.c_int32 * MAX_LEVELS),
+        ("W", C.c_int32 * MAX_LEVELS), ("num_levels", C.c_int32), ("B", C.c_int32), ("Cin", C.c_int32), ("n", C.c_int32),
+        ("g_pitch", C.c_int32), ("act_mode", C.c_int32), ("act_pitch", C.c_int32), ("n_slices", C.c_int32), ("plane_scale", C.c_float)
+    ]
+
+
+def pred_grad_slices(B, level_hw):
+    """Rows of `part` / `qpart` one dd3d_predictor_wgrad call needs (the rule of dd3d_predictor_grad_slices, for plans built without a device)."""
+    units = [B * h * ((w + PG_UNIT - 1) // PG_UNIT) for h, w in level_hw]
+    ups = max(1, (sum(units) + PG_TARGET_SLICES - 1) // PG_TARGET_SLICES)
+    return sum((u + ups - 1) // ups for u in units)
+
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
@@ -226,7 +250,8 @@ EXPORTS = [
     "dd3d_format_boxes3d", "dd3d_math_planes", "dd3d_split_planes", "dd3d_maxpool2x2_planes", "dd3d_maxpool2x2_planes_in", "dd3d_upsample2x_add_planes", "dd3d_ese_fused", "dd3d_stem_fused_f16x2", "dd3d_fold_range_flags", "dd3d_pack_readback",
     "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match", "dd3d_loss_assign", "dd3d_loss_terms", "dd3d_loss_layout",
     "dd3d_dense_depth_loss", "dd3d_dense_depth_loss_layout", "dd3d_loss_backward", "dd3d_loss_grad_layout",
-    "dd3d_dense_depth_loss_backward", "dd3d_dense_depth_grad_rows", "dd3d_dense_depth_grad_layout"
+    "dd3d_dense_depth_loss_backward", "dd3d_dense_depth_grad_rows", "dd3d_dense_depth_grad_layout",
+    "dd3d_predictor_wgrad", "dd3d_predictor_dgrad", "dd3d_predictor_grad_slices", "dd3d_pred_grad_layout"
 ]
 
 
@@ -305,6 +330,11 @@ def lib():
     L.dd3d_dense_depth_grad_rows.argtypes = [C.POINTER(DenseDepthLossArgs)]
     L.dd3d_dense_depth_grad_rows.restype = C.c_int64
     L.dd3d_dense_depth_grad_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_predictor_wgrad.argtypes = [C.POINTER(PredGradArgs), C.c_void_p]
+    L.dd3d_predictor_dgrad.argtypes = [C.POINTER(PredGradArgs), C.c_void_p]
+    L.dd3d_predictor_grad_slices.argtypes = [C.POINTER(PredGradArgs)]
+    L.dd3d_predictor_grad_slices.restype = C.c_int64
+    L.dd3d_pred_grad_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

@@ -119,14 +119,17 @@ class DD3D(nn.Module):
         self._evict_plans()
         return plan
 
-    def get_loss_plan(self, B, Hp, Wp, grads=False):
+    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
-        `grads`: the plan that also runs the loss backward (head-map gradients)."""
+        `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
+        backward behind it as well (parameter and tower-output gradients; implies `grads`)."""
         from dd3d_amd.engine.losses import LossPlan
-        key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + (("grads", ) if grads else ())
+        key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + \
+            (("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
         plan = self._plans.pop(key, None)
         if plan is None:
-            plan = LossPlan(self, B, Hp, Wp, grads=True) if grads else LossPlan(self, B, Hp, Wp)
+            plan = LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else LossPlan(self, B, Hp, Wp, grads=True) if grads else \
+                LossPlan(self, B, Hp, Wp)
             if self.use_graph:
                 plan.capture()
         self._plans[key] = plan
@@ -286,21 +289,26 @@ class DD3D(nn.Module):
     def _collect_extra(self, r, d, plan):
         pass
 
-    # ------------------------------------------------------------------ training losses (gradients: with respect to the head maps only)
+    # ------------------------------------------------------------------ training losses (gradients: head maps and the predictor layer)
     @torch.no_grad()
-    def compute_losses(self, batched_inputs, head_grads=False):
+    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
         reference: every norm layer uses its running statistics (the head maps are exactly this forward's), one process
         (reduce_sum is the identity).  With `head_grads` the result is (loss dict, grads): the gradient of the sum of the dict's values
         with respect to the head maps the losses read, as NCHW per-level tensors under the reference's names (logits<l>, box2d_reg<l>
-        -- post-ReLU --, centerness<l>, quat<l>, ctr<l>, depth<l>, size<l>, conf<l>, attr<l>, speed<l>); there is no backward through
-        the convolutions."""
+        -- post-ReLU --, centerness<l>, quat<l>, ctr<l>, depth<l>, size<l>, conf<l>, attr<l>, speed<l>).  With `predictor_grads` the
+        result is (loss dict, grads, param_grads): `grads` holds the same head-map gradients and also the gradient at the tower outputs
+        the predictors read (cls_tower_out<l>, box2d_tower_out<l>, box3d_tower_out<l>: (B, 256, h_l, w_l) float32); `param_grads` maps
+        the named_parameters() names of the predictor layer (the 3x3 predictors' weight and bias, the per-level Scale.scale and
+        Offset.bias) to float32 gradients of the parameter's shape.  The backward stops there: the towers, the FPN and the backbone
+        have none, and there is no optimiser, no batch-statistics norm and no model.train()."""
         from dd3d_amd.engine import relax_arithmetic
         gt = [x["instances"] for x in batched_inputs]
         while True:
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), grads=True) if head_grads else \
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), pred_grads=True) if predictor_grads else \
+                self.get_loss_plan(*self.canvas_size(batched_inputs), grads=True) if head_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs))
             plan.stage_gt(gt)
             self.stage_inputs(batched_inputs, plan=plan)  # (its flush ships the GT too)
@@ -313,6 +321,9 @@ class DD3D(nn.Module):
                     raise
                 continue
             losses = plan.loss_dict(int(rb.counts[0]))
+            if predictor_grads:
+                towers, params = plan.predictor_grads()
+                return losses, dict(plan.head_grads(), **towers), params
             return (losses, plan.head_grads()) if head_grads else losses
 
     @torch.no_grad()

@@ -1,7 +1,8 @@
 /*
  * dd3d_hip.h -- C ABI of the MI355X (gfx950) DD3D forward-path library  (libdd3d_hip.so): the forward, the evaluators' kernels and the
- * training losses (detector: dd3d_loss_*, with the head-map gradients of dd3d_loss_backward; depth pre-training: dd3d_dense_depth_loss,
- * with the gradient at the head's per-level maps of dd3d_dense_depth_loss_backward)
+ * training losses (detector: dd3d_loss_*, with the head-map gradients of dd3d_loss_backward and the predictor layer's backward below them,
+ * dd3d_predictor_wgrad / dd3d_predictor_dgrad; depth pre-training: dd3d_dense_depth_loss, with the gradient at the head's per-level maps
+ * of dd3d_dense_depth_loss_backward)
  *
  * The reference (TRI-ML/dd3d) has no FFI of its own for this path: it is pure Python and reaches
  * native code only through third-party wheels (cuDNN via torch, torchvision.ops.nms,
@@ -770,6 +771,69 @@ typedef struct dd3d_dense_depth_grad_args {  /* host memory */
 int dd3d_dense_depth_loss_backward(const dd3d_dense_depth_loss_args* args, const dd3d_dense_depth_grad_args* grads, void* stream);
 int64_t dd3d_dense_depth_grad_rows(const dd3d_dense_depth_loss_args* args);
 int dd3d_dense_depth_grad_layout(int64_t* out, int32_t n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the predictor layer (csrc/predictor_grads.hip): the 3x3, Cin -> n convolutions below the head maps (fcos2d.py:143-152,
+ * fcos3d.py:175-180, nuscenes_dd3d.py:371-374) with their per-level Scale / Offset.  One call covers one predictor GROUP: the predictors
+ * whose outputs share a head map (channels concatenated along n) and therefore one tower.  Forward, per level l:
+ *   map_l = clamp_lo((conv3x3(a_l, W_l) + b_l) * s_l + o_l)          W_l, b_l: the same arrays on every level that shares the module
+ * With G_l the head-map gradient dd3d_loss_backward wrote and g_l = G_l * [map_l > lo] on the channels with a finite lo (from the STORED
+ * map: an entry on its clamp gives 0, as torch.relu does), g_l = G_l elsewhere:
+ *   dw_level[l][n][ky][kx][c] = sum_{b,y,x} g_l[b,y,x,n] * a_l[b, y+ky-1, x+kx-1, c]       (zero padding; not scaled)
+ *   q[l][n] = sum_{b,y,x} g_l[b,y,x,n]        r[l][n] = sum_k dw_level[l][n][k] * W_l[n][k] + b_l[n] * q[l][n]   (= sum g_l * (conv + b))
+ *   dw[l] = sum_{m: w[m] == w[l]} s_m[n] * dw_level[m],   db[l][n] = sum_{m: w[m] == w[l]} s_m[n] * q[m][n]
+ *           written for the FIRST level l of each distinct filter pointer; the rows of the other levels are not touched
+ *   dscale[l][j] = sum_{n: slot[n] == j} r[l][n]   (d / d Scale_l of slot j)     doffset[l][j] = sum_{n: slot[n] == j} q[l][n]
+ *   da[l][b,y,x,c] = sum_{n,ky,kx} s_l[n] * g_l[b, y-ky+1, x-kx+1, n] * W_l[n][ky][kx][c]
+ * All sums are f32 sums of exact f32 products (the weight gradient on v_mfma_f32_32x32x2_f32, bitwise an fmaf chain) in a fixed order:
+ * per-slice partials, then one reducing launch -- no float atomics, two runs agree bit for bit.  Every word of the outputs named above
+ * is written (no memset needed); nothing beyond them is.
+ *
+ * act: the tower output as the plan holds it -- DD3D_PG_ACT_F32: f32 NHWC [B][H][W][act_pitch], pointer at the first channel;
+ *   DD3D_PG_ACT_F16X2 / _BF16X3: split planes [Cin/32][B*H*W][2 or 3][32] 16-bit terms (first chunk of the slice), halves of
+ *   value * plane_scale resp. bf16 terms, decoded as the convolutions decode them.
+ * dd3d_predictor_wgrad: dw_level, q, r, dw, db, dscale, doffset (four launches).  dd3d_predictor_dgrad: da (one launch; reads g, map,
+ *   lo, scale, w only).  Both after dd3d_loss_backward on the same stream; safe under stream capture.
+ * dd3d_predictor_grad_slices: rows of `part` / `qpart` a weight-gradient call on `args` needs (host only; -1 on bad args).
+ * dd3d_pred_grad_layout: sizeof(dd3d_pred_grad_args) and the byte offsets of its fields (layout check of the bindings; host only).
+ * Rejected: Cin not a multiple of 32, pitches not a multiple of 4 or too small, n outside 1 .. DD3D_PG_MAX_N, null pointers.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_PG_MAX_SLOTS 8
+#define DD3D_PG_MAX_N 256
+#define DD3D_PG_UNIT 64
+#define DD3D_PG_ACT_F32 0
+#define DD3D_PG_ACT_F16X2 1
+#define DD3D_PG_ACT_BF16X3 2
+typedef struct dd3d_pred_grad_args {        /* host memory; every pointer is device memory */
+  const void* act[DD3D_MAX_LEVELS];
+  const float* g[DD3D_MAX_LEVELS];          /* [B][H][W][g_pitch] */
+  const float* map[DD3D_MAX_LEVELS];        /* the stored head map, layout of g; read where lo is finite; may be NULL when lo is */
+  const float* w[DD3D_MAX_LEVELS];          /* [n][3][3][Cin] */
+  const float* bias[DD3D_MAX_LEVELS];       /* [n]; zeros where a module has no bias */
+  const float* scale[DD3D_MAX_LEVELS];      /* [n] s_l */
+  float* da[DD3D_MAX_LEVELS];               /* [B][H][W][Cin] f32 */
+  const float* lo;                          /* [n] lower clamp of the forward (-inf: none), or NULL */
+  const int32_t* slot;                      /* [n] Scale / Offset slot of a channel, 0 .. DD3D_PG_MAX_SLOTS - 1, or -1; or NULL */
+  float* part;                              /* scratch [n_slices][n][9 * Cin] */
+  float* qpart;                             /* scratch [n_slices][n] */
+  float* dw_level;                          /* [num_levels][n][9 * Cin] */
+  float* dw;                                /* [num_levels][n][9 * Cin] */
+  float* db;                                /* [num_levels][n] */
+  float* q;                                 /* [num_levels][n] */
+  float* r;                                 /* [num_levels][n] */
+  float* dscale;                            /* [num_levels][DD3D_PG_MAX_SLOTS] */
+  float* doffset;                           /* [num_levels][DD3D_PG_MAX_SLOTS] */
+  int32_t H[DD3D_MAX_LEVELS], W[DD3D_MAX_LEVELS];
+  int32_t num_levels, B, Cin, n, g_pitch;
+  int32_t act_mode;                         /* DD3D_PG_ACT_* */
+  int32_t act_pitch;                        /* DD3D_PG_ACT_F32: floats per pixel */
+  int32_t n_slices;                         /* rows of part / qpart */
+  float plane_scale;                        /* DD3D_PG_ACT_F16X2: the planes hold value * plane_scale (a power of two) */
+} dd3d_pred_grad_args;
+int dd3d_predictor_wgrad(const dd3d_pred_grad_args* args, void* stream);
+int dd3d_predictor_dgrad(const dd3d_pred_grad_args* args, void* stream);
+int64_t dd3d_predictor_grad_slices(const dd3d_pred_grad_args* args);
+int dd3d_pred_grad_layout(int64_t* out, int32_t n);
 
 #ifdef __cplusplus
 }
