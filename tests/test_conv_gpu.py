@@ -58,7 +58,7 @@ def test_conv_matches_torch(hiplib, case):
     from dd3d_amd.engine import ConvOp, PlanBase, pack_filter
     name, B, H, W, Cin, Cout, k, stride, pad, relu, use_res, tile, splitk = case
     math = hip.MATH_BF16X3 if name.startswith("x3_") else hip.MATH_F32
-    g = torch.Generator().manual_seed(hash(name) % 1000)
+    g = torch.Generator().manual_seed(sum(map(ord, name)) % 1000)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k)**0.5
     scale = torch.rand(Cout, generator=g) + 0.5
