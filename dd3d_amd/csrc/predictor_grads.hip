@@ -20,6 +20,7 @@
 // scaled gradient rows [3][18][n] in LDS; every thread walks (tap, n) with its 16 accumulators, reading the filter row-coalesced from
 // L2 and the gradient as LDS broadcasts (plain fmaf: K = 9 n is short and the kernel is bound by its store).  A block whose staged
 // gradient is all zero stores zeros.
+#include "act_load.h"
 #include "common.h"
 
 DD3D_NOTE_BUILD_FLAGS
@@ -55,27 +56,6 @@ inline void plan_slices(const dd3d_pred_grad_args& a, PredK& k) {
     k.dunit_off[l + 1] = k.dunit_off[l] + a.B * a.H[l] * ceil_div(a.W[l], PG_DP);
   }
   for (int l = a.num_levels; l < DD3D_MAX_LEVELS; ++l) k.slice_off[l + 1] = k.slice_off[l], k.dunit_off[l + 1] = k.dunit_off[l];
-}
-
-// ---- activation loaders: the value of channel c at pixel `pix` of a level with `npix` pixels, from the storage the plan keeps
-template <int MODE>
-__device__ __forceinline__ float load_act(const void* base, long npix, long pix, int c, int pitch, float inv_scale);
-template <>
-__device__ __forceinline__ float load_act<DD3D_PG_ACT_F32>(const void* base, long, long pix, int c, int pitch, float) {
-  return reinterpret_cast<const float*>(base)[pix * pitch + c];
-}
-template <>
-__device__ __forceinline__ float load_act<DD3D_PG_ACT_F16X2>(const void* base, long npix, long pix, int c, int, float inv_scale) {
-  // [c / 32][pixel][hi, lo][32] halves of value * plane_scale: (hi + lo) / plane_scale, as conv_common.h::unpack_terms decodes them
-  const _Float16* p = reinterpret_cast<const _Float16*>(base) + ((long)(c >> 5) * npix + pix) * 64 + (c & 31);
-  return ((float)p[0] + (float)p[32]) * inv_scale;
-}
-template <>
-__device__ __forceinline__ float load_act<DD3D_PG_ACT_BF16X3>(const void* base, long npix, long pix, int c, int, float) {
-  // [c / 32][pixel][hi, mid, lo][32] bf16 terms, largest first: (hi + mid) + lo
-  const unsigned short* p = reinterpret_cast<const unsigned short*>(base) + ((long)(c >> 5) * npix + pix) * 96 + (c & 31);
-  const float hi = __uint_as_float((unsigned)p[0] << 16), mid = __uint_as_float((unsigned)p[32] << 16), lo = __uint_as_float((unsigned)p[64] << 16);
-  return (hi + mid) + lo;
 }
 
 // g_l of the header: the head-map gradient, 0 where a clamped channel's stored map sits on its clamp

@@ -124,7 +124,7 @@ class ForwardPlan(PlanBase, BackboneLowering):
         return t[..., :3].permute(0, 3, 1, 2)
 
     # ------------------------------------------------------------------ heads (fcos2d.py:130-156, fcos3d.py:160-188)
-    def _heads(self, model, feats):
+    def _heads(self, model, feats, keep_tower_outputs=False):
         dev = self.device
         h2, h3 = model.fcos2d_head, (None if model.only_box2d else model.fcos3d_head)
         L = len(feats)
@@ -132,23 +132,33 @@ class ForwardPlan(PlanBase, BackboneLowering):
         nt = len(towers)
         Cf = feats[0].C
         depth = max(len(t) for _, t in towers)
-        ping = [self.buf(f"towerA.{l}", f.B, f.H, f.W, nt * Cf, kind="planes") for l, f in enumerate(feats)]  # conv -> conv only
-        pong = [self.buf(f"towerB.{l}", f.B, f.H, f.W, nt * Cf, kind="planes") for l, f in enumerate(feats)]
+        # A plan built for tower gradients (LossPlan(tower_grads=True)) gives every tower layer its own output buffer, so that all
+        # stored outputs survive to the backward; every other plan keeps the two ping / pong buffers.
+        keep_all = bool(keep_tower_outputs)
+        tbuf = lambda name: [self.buf(f"{name}.{l}", f.B, f.H, f.W, nt * Cf, kind="planes") for l, f in enumerate(feats)]  # conv -> conv only
+        if not keep_all:
+            ping, pong = tbuf("towerA"), tbuf("towerB")
         cur = [[feats[l] for _ in range(nt)] for l in range(L)]  # current input view per (level, tower)
+        # (tower name, layer) -> what the tower backward (engine.losses) needs: module, per-level norms, device scale vectors, input / output views
+        self.tower_info = {} if keep_all else None
         for i in range(depth):
-            dstbufs = ping if i % 2 == 0 else pong
+            dstbufs = tbuf(f"towerL{i}") if keep_all else ping if i % 2 == 0 else pong
             segs, meta = [], None
             for t, (tname, tower) in enumerate(towers):
                 if i >= len(tower):
                     continue
                 conv = tower[i]
                 w, meta = self.pack(conv.weight)
+                info = dict(conv=conv, index=t, norms=[], scales=[], x=[], y=[])
+                if keep_all:
+                    self.tower_info[(tname, i)] = info
                 for l in range(L):
                     # ModuleListDial: level l uses norm[l] (normalization.py:30-40)
                     norm = conv.norm[l] if isinstance(conv.norm, torch.nn.ModuleList) else conv.norm
                     scale, shift = fold_norm(conv, norm)
                     out = dstbufs[l].view(t * Cf, Cf)
                     segs.append({"in": cur[l][t], "out": out, "w": w, "scale": self._vec(scale), "bias": self._vec(shift)})
+                    info["norms"].append(norm), info["scales"].append(segs[-1]["scale"]), info["x"].append(cur[l][t]), info["y"].append(out)
                     cur[l][t] = out
             self.ops.append(ConvOp(self, meta, 1, 1, segs, relu=True, name=f"towers.{i}"))
         self.tower_out = cur

@@ -1,7 +1,8 @@
 """Loss engine: target assignment and the training loss dict of DD3D / NuscenesDD3D on the MI355X, and on request the gradient of
 the dict's weighted sum with respect to the head maps (csrc/loss_grads.hip) and, one layer further down, with respect to the predictor
-layer's parameters and the tower outputs it reads (csrc/predictor_grads.hip).  The backward stops there: towers, FPN and backbone have
-none, and there is no optimiser, batch-statistics norm or model.train().
+layer's parameters and the tower outputs it reads (csrc/predictor_grads.hip), and one layer further again through the head towers to
+their parameters and the FPN outputs (csrc/tower_grads.hip).  The backward stops there: FPN and backbone have none, and there is no
+optimiser, batch-statistics norm or model.train().
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -322,12 +323,113 @@ class PredGroupGrads:
         return all(bool((t[n:] == fill).all()) for t, n in self._raw)
 
 
+def act_binding(plan, view):
+    """(DD3D_PG_ACT_* mode, device address, pitch, plane scale) of the storage a plan keeps `view` in: its split planes where it has
+    them, else f32 NHWC.  The reduced modes have no loader (pred_act_mode names them)."""
+    if view.np and plan.use_planes:
+        return pred_act_mode(plan), view.pptr, 0, float(view.buf.plane_scale)
+    return hip.PG_ACT_F32, view.ptr, int(view.pitch), 1.0
+
+
+class TowerLayerGrads:
+    """Buffers and dd3d_tower_grad_args of one tower layer over all levels.
+
+    `x`, `y`: per level (mode, device address, pitch, plane scale) of the layer's input and stored output (one mode per side); `g`:
+    per-level NHWC gradient tensors of pitch `g_pitch`; `w`: the [Cout, 3, 3, Cin] filter; `scale`: per-level [Cout]; `da_add`: per-level
+    [B, h, w, Cin] tensors or None; `slab`: (part, qpart) shared with other layers that run in stream order, or None to allocate them.
+    Outputs are allocated here, filled with `fill` and followed by `guard` words of it."""
+    def __init__(self, device, B, level_hw, Cin, Cout, x, y, g, g_pitch, w, scale, da_add=None, slab=None, fill=0.0, guard=0, dgrad_rows=0):
+        L = len(level_hw)
+        self.B, self.level_hw, self.Cin, self.Cout, self.L = B, list(level_hw), Cin, Cout, L
+        self.keep = (g, w, scale, da_add, slab)
+        a = hip.TowerGradArgs()
+        self._raw = []
+
+        def out(*shape):
+            numel = int(np.prod(shape))
+            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
+            self._raw.append((t, numel))
+            return t[:numel].view(*shape)
+
+        K9 = 9 * Cin
+        self.n_slices = hip.tower_grad_slices(B, level_hw, Cin, Cout)
+        if slab is None:
+            slab = (out(self.n_slices, Cout, K9), out(self.n_slices, Cout))
+        self.part, self.qpart = slab
+        assert self.part.numel() >= self.n_slices * Cout * K9 and self.qpart.numel() >= self.n_slices * Cout
+        self.dw_level, self.dw = out(L, Cout, K9), out(Cout, K9)
+        self.q, self.r = out(L, Cout), out(L, Cout)
+        self.da = [out(B, h, w_, Cin) for h, w_ in level_hw]
+        for l, (h, w_) in enumerate(level_hw):
+            a.x[l], a.y[l] = x[l][1] or None, y[l][1] or None
+            a.g[l], a.scale[l], a.da[l] = g[l].data_ptr(), scale[l].data_ptr(), self.da[l].data_ptr()
+            a.da_add[l] = da_add[l].data_ptr() if da_add is not None else None
+            a.H[l], a.W[l] = int(h), int(w_)
+        a.w = w.data_ptr()
+        a.part, a.qpart, a.dw_level, a.dw = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw))
+        a.q, a.r = self.q.data_ptr(), self.r.data_ptr()
+        a.num_levels, a.B, a.Cin, a.Cout, a.g_pitch = L, int(B), int(Cin), int(Cout), int(g_pitch)
+        a.x_mode, a.x_pitch, a.x_plane_scale = int(x[0][0]), int(x[0][2]), float(x[0][3])
+        a.y_mode, a.y_pitch, a.y_plane_scale = int(y[0][0]), int(y[0][2]), float(y[0][3])
+        assert all(v[0] == x[0][0] and v[2:] == x[0][2:] for v in x) and all(v[0] == y[0][0] and v[2:] == y[0][2:] for v in y)
+        a.n_slices, a.dgrad_rows = self.n_slices, int(dgrad_rows)
+        self.args = a
+
+    def launch(self, lib, st):
+        hip.check(lib.dd3d_tower_wgrad(C.byref(self.args), st), "tower_wgrad")
+        hip.check(lib.dd3d_tower_dgrad(C.byref(self.args), st), "tower_dgrad")
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
+def norm_param_grads(conv, norm, scale, q, r):
+    """Gradients of one level's share of a tower layer's per-channel parameters from the kernels' sums q = sum g and r = sum g * conv:
+    {"norm.weight", "norm.bias", "bias"} as far as the modules have them as parameters.  The forward is layers.fold_norm's:
+    y = (conv + b - mean) * w * rstd + beta, with w * rstd = `scale`; without a norm y = conv + b."""
+    out = {}
+    b = conv.bias.detach().float().to(q.device) if conv.bias is not None else None
+    if norm is not None and isinstance(norm.weight, torch.nn.Parameter):
+        rstd = torch.rsqrt(norm.running_var.float() + norm.eps).to(q.device)
+        centre = -norm.running_mean.float().to(q.device) if b is None else b - norm.running_mean.float().to(q.device)
+        out["norm.weight"] = rstd * (r + centre * q)
+        out["norm.bias"] = q.clone()
+    if b is not None:
+        out["bias"] = scale.to(q.device) * q if norm is not None else q.clone()
+    return out
+
+
+def assemble_tower_grads(model, layers, feature_grads):
+    """TowerLayerGrads of every (tower, layer) -> ({feature<l>: NCHW}, {parameter name: gradient}); parameters shared by several
+    levels get the sum over them, in level order."""
+    names = {id(p): k for k, p in model.named_parameters()}
+    feats = {f"feature{l}": d.permute(0, 3, 1, 2).clone() for l, d in enumerate(feature_grads)}
+    params = {}
+
+    def add(p, v):
+        if id(p) in names:
+            params[names[id(p)]] = v if names[id(p)] not in params else params[names[id(p)]] + v
+
+    for lay in layers.values():
+        conv = lay.conv
+        add(conv.weight, lay.dw.view(lay.Cout, 3, 3, lay.Cin).permute(0, 3, 1, 2).contiguous())
+        for l in range(lay.L):
+            norm = lay.norms[l]
+            got = norm_param_grads(conv, norm, lay.keep[2][l], lay.q[l], lay.r[l])
+            if "norm.weight" in got:
+                add(norm.weight, got["norm.weight"]), add(norm.bias, got["norm.bias"])
+            if "bias" in got:
+                add(conv.bias, got["bias"])
+    return feats, params
+
+
 class LossPlan(ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
-    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False):
+    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False):
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
-        self.pred_grads = bool(pred_grads)
+        self.keep_tower_outputs = bool(tower_grads)  # (`tower_grads` itself is the read-out method)
+        self.pred_grads = bool(pred_grads) or self.keep_tower_outputs
         self.grads = bool(grads) or self.pred_grads
         check_loss_config(model.cfg)
         from dd3d_amd.engine.tiling import default_tile_policy
@@ -335,7 +437,7 @@ class LossPlan(ForwardPlan):
         self.exchange, self.camera_sharded, self.has_bev_inputs = False, False, False
         self.adopt_weight_store(model)
         self._trunk(model, B, Hp, Wp)
-        self._heads(model, self.features)
+        self._heads(model, self.features, keep_tower_outputs=self.keep_tower_outputs)
         self._losses(model, max_gt)
 
     def _losses(self, model, max_gt):
@@ -387,6 +489,8 @@ class LossPlan(ForwardPlan):
             self._loss_grads(a)
         if self.pred_grads:
             self._pred_grads(model)
+        if self.keep_tower_outputs:
+            self._tower_grads(model)
 
     def _loss_grads(self, a):
         """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
@@ -471,6 +575,55 @@ class LossPlan(ForwardPlan):
                     if offsets is not None:
                         params[names[id(offsets[l].bias)]] = grp.doffset[l, j:j + 1].clone()
         return towers, params
+
+    def _tower_grads(self, model):
+        """The towers' backward behind the predictor groups: one weight-gradient and one input-gradient call per (tower, layer), last
+        layer first, on the main stream -- still one hipGraph.  Layer i reads layer i + 1's input gradient (the last layer the predictor
+        group's); the first layers of the towers add up, in tower order, to the gradient at the FPN outputs.  One slab of weight-gradient
+        partials serves every call: they run in stream order."""
+        dev, L = self.device, len(self.features)
+        level_hw = [(f.H, f.W) for f in self.features]
+        group_of = {grp.tower: grp for grp in self.pred_groups.values()}
+        towers = []
+        for (tname, i) in self.tower_info:
+            if tname not in towers:
+                towers.append(tname)
+        depth = {t: 1 + max(i for (tn, i) in self.tower_info if tn == t) for t in towers}
+        if set(group_of) - set(towers):
+            raise NotImplementedError(f"tower gradients need at least one layer in every tower (none in {sorted(set(group_of) - set(towers))})")
+        shapes = {(int(v["conv"].weight.shape[1]), int(v["conv"].weight.shape[0])) for v in self.tower_info.values()}
+        n_slices = max(hip.tower_grad_slices(self.B, level_hw, ci, co) for ci, co in shapes)
+        words = max(ci * co for ci, co in shapes) * 9
+        cmax = max(co for _, co in shapes)
+        alloc = torch.empty if self.dry_run else torch.zeros  # (a dry-run plan never touches the slab)
+        self.tower_slab = (alloc(n_slices * words, dtype=torch.float32, device=dev), alloc(n_slices * cmax, dtype=torch.float32, device=dev))
+        self.tower_layers = {}
+        feature_da = None
+        for tname in towers:
+            g, g_pitch = group_of[tname].da, group_of[tname].Cin
+            for i in reversed(range(depth[tname])):
+                info = self.tower_info[(tname, i)]
+                conv = info["conv"]
+                Cout, Cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
+                w = conv.weight.detach().float().permute(0, 2, 3, 1).contiguous().to(dev)
+                lay = TowerLayerGrads(dev, self.B, level_hw, Cin, Cout, [act_binding(self, v) for v in info["x"]],
+                                      [act_binding(self, v) for v in info["y"]], g, g_pitch, w, info["scales"],
+                                      da_add=feature_da if i == 0 else None, slab=self.tower_slab)
+                lay.conv, lay.norms, lay.tower, lay.index = conv, info["norms"], tname, i
+                self.tower_layers[(tname, i)] = lay
+                self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), f"tower_grads.{tname}.{i}",
+                                       dict(kind="tower_grads", tower=tname, layer=i)))
+                g, g_pitch = lay.da, Cin
+            feature_da = g
+        self.feature_grads = feature_da
+
+    def tower_grads(self):
+        """(FPN-output gradients, tower parameter gradients) of the last run, copies: {feature<l>: (B, C, h_l, w_l)} and {name in
+        model.named_parameters(): tensor of the parameter's shape}, float32.  A filter's gradient is the kernels' dw; the few per-channel
+        products of a norm's weight (rstd * (r + (b_conv - mean) * q)) and the sums of q over the levels are torch ops here."""
+        if not self.keep_tower_outputs:
+            raise RuntimeError("this LossPlan was built without tower_grads=True")
+        return assemble_tower_grads(self.model, self.tower_layers, self.feature_grads)
 
     def head_grads(self):
         """The gradients of the last run as NCHW per-level tensors (copies) under the keys of the reference's head maps."""

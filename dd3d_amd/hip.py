@@ -243,6 +243,30 @@ def pred_grad_slices(B, level_hw):
     return sum((u + ups - 1) // ups for u in units)
 
 
+TG_MAX_C, TG_UNIT, TG_MIN_UNITS_PER_SLICE, TG_SLAB_BYTES, TG_MIN_TILES = 256, 64, 4, 160 << 20, 512
+
+
+class TowerGradArgs(C.Structure):
+    """`dd3d_tower_grad_args`."""
+    _fields_ = [
+        ("x", C.c_void_p * MAX_LEVELS), ("y", C.c_void_p * MAX_LEVELS), ("g", C.c_void_p * MAX_LEVELS), ("scale", C.c_void_p * MAX_LEVELS),
+        ("da_add", C.c_void_p * MAX_LEVELS), ("da", C.c_void_p * MAX_LEVELS), ("w", C.c_void_p), ("part", C.c_void_p), ("qpart", C.c_void_p),
+        ("dw_level", C.c_void_p), ("dw", C.c_void_p), ("q", C.c_void_p), ("r", C.c_void_p), ("H", C.c_int32 * MAX_LEVELS),
+        ("W", C.c_int32 * MAX_LEVELS), ("num_levels", C.c_int32), ("B", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32),
+        ("g_pitch", C.c_int32), ("x_mode", C.c_int32), ("x_pitch", C.c_int32), ("y_mode", C.c_int32), ("y_pitch", C.c_int32),
+        ("n_slices", C.c_int32), ("dgrad_rows", C.c_int32), ("x_plane_scale", C.c_float), ("y_plane_scale", C.c_float)
+    ]
+
+
+def tower_grad_slices(B, level_hw, Cin, Cout):
+    """Rows of `part` / `qpart` one dd3d_tower_wgrad call needs (the rule of dd3d_tower_grad_slices, for plans built without a device):
+    at least TG_MIN_UNITS_PER_SLICE 64-pixel units per slice, more once the slab would pass TG_SLAB_BYTES."""
+    units = [B * h * ((w + TG_UNIT - 1) // TG_UNIT) for h, w in level_hw]
+    max_slices = max(1, TG_SLAB_BYTES // (Cout * 9 * Cin * 4))
+    ups = max(TG_MIN_UNITS_PER_SLICE, (sum(units) + max_slices - 1) // max_slices)
+    return sum((u + ups - 1) // ups for u in units)
+
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
@@ -251,7 +275,8 @@ EXPORTS = [
     "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match", "dd3d_loss_assign", "dd3d_loss_terms", "dd3d_loss_layout",
     "dd3d_dense_depth_loss", "dd3d_dense_depth_loss_layout", "dd3d_loss_backward", "dd3d_loss_grad_layout",
     "dd3d_dense_depth_loss_backward", "dd3d_dense_depth_grad_rows", "dd3d_dense_depth_grad_layout",
-    "dd3d_predictor_wgrad", "dd3d_predictor_dgrad", "dd3d_predictor_grad_slices", "dd3d_pred_grad_layout"
+    "dd3d_predictor_wgrad", "dd3d_predictor_dgrad", "dd3d_predictor_grad_slices", "dd3d_pred_grad_layout",
+    "dd3d_tower_wgrad", "dd3d_tower_dgrad", "dd3d_tower_grad_slices", "dd3d_tower_grad_layout"
 ]
 
 
@@ -335,6 +360,11 @@ def lib():
     L.dd3d_predictor_grad_slices.argtypes = [C.POINTER(PredGradArgs)]
     L.dd3d_predictor_grad_slices.restype = C.c_int64
     L.dd3d_pred_grad_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_tower_wgrad.argtypes = [C.POINTER(TowerGradArgs), C.c_void_p]
+    L.dd3d_tower_dgrad.argtypes = [C.POINTER(TowerGradArgs), C.c_void_p]
+    L.dd3d_tower_grad_slices.argtypes = [C.POINTER(TowerGradArgs)]
+    L.dd3d_tower_grad_slices.restype = C.c_int64
+    L.dd3d_tower_grad_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

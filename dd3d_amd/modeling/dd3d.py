@@ -119,17 +119,18 @@ class DD3D(nn.Module):
         self._evict_plans()
         return plan
 
-    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False):
+    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
         `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
-        backward behind it as well (parameter and tower-output gradients; implies `grads`)."""
+        backward behind it as well (parameter and tower-output gradients; implies `grads`); `tower_grads`: the plan that goes on through
+        the head towers (their parameter gradients and the gradient at the FPN outputs; implies `pred_grads`)."""
         from dd3d_amd.engine.losses import LossPlan
         key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + \
-            (("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
+            (("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
         plan = self._plans.pop(key, None)
         if plan is None:
-            plan = LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else LossPlan(self, B, Hp, Wp, grads=True) if grads else \
-                LossPlan(self, B, Hp, Wp)
+            plan = LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
+                LossPlan(self, B, Hp, Wp, grads=True) if grads else LossPlan(self, B, Hp, Wp)
             if self.use_graph:
                 plan.capture()
         self._plans[key] = plan
@@ -291,7 +292,7 @@ class DD3D(nn.Module):
 
     # ------------------------------------------------------------------ training losses (gradients: head maps and the predictor layer)
     @torch.no_grad()
-    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False):
+    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
@@ -302,12 +303,16 @@ class DD3D(nn.Module):
         result is (loss dict, grads, param_grads): `grads` holds the same head-map gradients and also the gradient at the tower outputs
         the predictors read (cls_tower_out<l>, box2d_tower_out<l>, box3d_tower_out<l>: (B, 256, h_l, w_l) float32); `param_grads` maps
         the named_parameters() names of the predictor layer (the 3x3 predictors' weight and bias, the per-level Scale.scale and
-        Offset.bias) to float32 gradients of the parameter's shape.  The backward stops there: the towers, the FPN and the backbone
-        have none, and there is no optimiser, no batch-statistics norm and no model.train()."""
+        Offset.bias) to float32 gradients of the parameter's shape.  With `tower_grads` the result has the same form and the backward
+        goes on through the head towers: `grads` also holds the gradient at the FPN outputs the heads read (feature<l>: (B, 256, h_l,
+        w_l)), `param_grads` also the tower parameters (every tower filter; a BN tower's per-level norm weight and bias; a norm-less
+        tower's conv bias; a FrozenBN tower's norm has no parameters).  The backward stops there: the FPN and the backbone have none,
+        and there is no optimiser, no batch-statistics norm and no model.train()."""
         from dd3d_amd.engine import relax_arithmetic
         gt = [x["instances"] for x in batched_inputs]
         while True:
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), pred_grads=True) if predictor_grads else \
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), tower_grads=True) if tower_grads else \
+                self.get_loss_plan(*self.canvas_size(batched_inputs), pred_grads=True) if predictor_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), grads=True) if head_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs))
             plan.stage_gt(gt)
@@ -321,8 +326,11 @@ class DD3D(nn.Module):
                     raise
                 continue
             losses = plan.loss_dict(int(rb.counts[0]))
-            if predictor_grads:
+            if predictor_grads or tower_grads:
                 towers, params = plan.predictor_grads()
+                if tower_grads:
+                    feats, tparams = plan.tower_grads()
+                    towers, params = dict(towers, **feats), dict(params, **tparams)
                 return losses, dict(plan.head_grads(), **towers), params
             return (losses, plan.head_grads()) if head_grads else losses
 

@@ -1,7 +1,7 @@
 /*
  * dd3d_hip.h -- C ABI of the MI355X (gfx950) DD3D forward-path library  (libdd3d_hip.so): the forward, the evaluators' kernels and the
  * training losses (detector: dd3d_loss_*, with the head-map gradients of dd3d_loss_backward and the predictor layer's backward below them,
- * dd3d_predictor_wgrad / dd3d_predictor_dgrad; depth pre-training: dd3d_dense_depth_loss, with the gradient at the head's per-level maps
+ * dd3d_predictor_wgrad / dd3d_predictor_dgrad, and the head towers' below those, dd3d_tower_wgrad / dd3d_tower_dgrad; depth pre-training: dd3d_dense_depth_loss, with the gradient at the head's per-level maps
  * of dd3d_dense_depth_loss_backward)
  *
  * The reference (TRI-ML/dd3d) has no FFI of its own for this path: it is pure Python and reaches
@@ -834,6 +834,66 @@ int dd3d_predictor_wgrad(const dd3d_pred_grad_args* args, void* stream);
 int dd3d_predictor_dgrad(const dd3d_pred_grad_args* args, void* stream);
 int64_t dd3d_predictor_grad_slices(const dd3d_pred_grad_args* args);
 int dd3d_pred_grad_layout(int64_t* out, int32_t n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Backward of one head-tower layer over all pyramid levels (csrc/tower_grads.hip): the 3x3, Cin -> Cout convolution of a tower
+ * (fcos2d.py:130-141, fcos3d.py:160-173) with its per-level folded norm and ReLU.  Forward, per level l, W shared by the levels:
+ *   y_l = relu(s_l * conv3x3(x_l, W) + t_l)                     (s_l, t_l): layers.fold_norm of the level's norm, running statistics
+ * With G_l the gradient at y_l and g_l = G_l * [y_l > 0], the mask taken from the STORED y_l (an entry on the clamp gives 0):
+ *   dw_level[l][n][ky][kx][c] = sum_{b,y,x} g_l[b,y,x,n] * x_l[b, y+ky-1, x+kx-1, c]        (zero padding; not scaled)
+ *   dw[n][k] = sum_l s_l[n] * dw_level[l][n][k]                  one fmaf per level, in level order
+ *   q[l][n] = sum_{b,y,x} g_l[b,y,x,n]          r[l][n] = sum_k dw_level[l][n][k] * W[n][k]     (= sum g_l * conv; no division by s_l)
+ *   da[l][b,y,x,c] = da_add[l][b,y,x,c] + sum_{n,ky,kx} s_l[n] * g_l[b, y-ky+1, x-kx+1, n] * W[n][ky][kx][c]
+ * Both are GEMMs on v_mfma_f32_32x32x2_f32 (exact f32 products, f32 accumulation, bitwise an fmaf chain in k order): the weight
+ * gradient with M = Cout, N = 9 Cin, K = the pixels of a slice, per-slice partials summed in slice order by a second launch; the input
+ * gradient with M = pixels, N = Cin, K = 9 Cout, one accumulator per 32-channel chunk of Cout (its 288 terms in (tap, n) order), the
+ * chunks added in chunk order.  A zero or masked g_l entry enters both as an exact zero whatever s_l holds.  No float atomics: every sum
+ * has one writer and a fixed order, two runs agree bit for bit, whichever pixel tile the input gradient picks.  Every word of dw_level,
+ * dw, q, r and da is written (no memset needed); nothing beyond them and the scratch rows in use is.
+ *
+ * x, y: the layer's input and stored output as the plan holds them, each in its own storage (DD3D_PG_ACT_*: f32 NHWC with a pitch, or
+ *   split planes of the slice's first chunk; f16x2 planes hold value * plane_scale).  g, da, da_add: f32 NHWC, pitches g_pitch / Cin / Cin.
+ * part / qpart: dd3d_tower_grad_slices(args) rows (host only; it reads B, H, W, num_levels, Cin and Cout alone, no pointer needs to
+ *   be set).  The count grows with the pixel count (four 64-pixel units per slice at least) until the slab reaches DD3D_TG_SLAB_BYTES
+ *   (+ at most one row per level), from where the units per slice grow instead.
+ * dgrad_rows: rows of the input gradient's 16-pixel-wide tile, 2, 4 or 8; 0 lets the call choose (the largest that still gives
+ *   DD3D_TG_MIN_TILES blocks).  The result does not depend on it.
+ * dd3d_tower_wgrad: dw_level, dw, q, r (three launches).  dd3d_tower_dgrad: da (one launch; reads g, y, scale, w, da_add only).  Safe
+ *   under stream capture.  dd3d_tower_grad_layout: sizeof and field offsets (layout check of the bindings; host only).
+ * Rejected (-1, dd3d_last_error starts with the entry point's name): Cin or Cout not a multiple of 32 or above DD3D_TG_MAX_C, pitches
+ *   not a multiple of 4 or too small, unknown storages, null pointers, too few slab rows, dgrad_rows outside {0, 2, 4, 8}.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_TG_MAX_C 256
+#define DD3D_TG_UNIT 64
+#define DD3D_TG_MIN_UNITS_PER_SLICE 4
+#define DD3D_TG_SLAB_BYTES (160ll << 20)
+#define DD3D_TG_MIN_TILES 512
+typedef struct dd3d_tower_grad_args {       /* host memory; every pointer is device memory */
+  const void* x[DD3D_MAX_LEVELS];           /* layer input, storage x_mode */
+  const void* y[DD3D_MAX_LEVELS];           /* stored layer output (after the ReLU), storage y_mode */
+  const float* g[DD3D_MAX_LEVELS];          /* gradient at y: [B][H][W][g_pitch] */
+  const float* scale[DD3D_MAX_LEVELS];      /* [Cout] s_l */
+  const float* da_add[DD3D_MAX_LEVELS];     /* [B][H][W][Cin], or all NULL */
+  float* da[DD3D_MAX_LEVELS];               /* [B][H][W][Cin] */
+  const float* w;                           /* [Cout][3][3][Cin] */
+  float* part;                              /* scratch [n_slices][Cout][9 * Cin] */
+  float* qpart;                             /* scratch [n_slices][Cout] */
+  float* dw_level;                          /* [num_levels][Cout][9 * Cin] */
+  float* dw;                                /* [Cout][9 * Cin] */
+  float* q;                                 /* [num_levels][Cout] */
+  float* r;                                 /* [num_levels][Cout] */
+  int32_t H[DD3D_MAX_LEVELS], W[DD3D_MAX_LEVELS];
+  int32_t num_levels, B, Cin, Cout, g_pitch;
+  int32_t x_mode, x_pitch;                  /* DD3D_PG_ACT_*; floats per pixel (DD3D_PG_ACT_F32) */
+  int32_t y_mode, y_pitch;
+  int32_t n_slices;                         /* rows of part / qpart */
+  int32_t dgrad_rows;
+  float x_plane_scale, y_plane_scale;       /* DD3D_PG_ACT_F16X2 */
+} dd3d_tower_grad_args;
+int dd3d_tower_wgrad(const dd3d_tower_grad_args* args, void* stream);
+int dd3d_tower_dgrad(const dd3d_tower_grad_args* args, void* stream);
+int64_t dd3d_tower_grad_slices(const dd3d_tower_grad_args* args);
+int dd3d_tower_grad_layout(int64_t* out, int32_t n);
 
 #ifdef __cplusplus
 }
