@@ -1,8 +1,9 @@
 """Loss engine: target assignment and the training loss dict of DD3D / NuscenesDD3D on the MI355X, and on request the gradient of
 the dict's weighted sum with respect to the head maps (csrc/loss_grads.hip) and, one layer further down, with respect to the predictor
 layer's parameters and the tower outputs it reads (csrc/predictor_grads.hip), and one layer further again through the head towers to
-their parameters and the FPN outputs (csrc/tower_grads.hip).  The backward stops there: FPN and backbone have none, and there is no
-optimiser, batch-statistics norm or model.train().
+their parameters and the FPN outputs (csrc/tower_grads.hip), and one stage further through the FPN to its parameters and the backbone's
+output features (csrc/fpn_grads.hip).  The backward stops there: the backbone has none, and there is no optimiser, batch-statistics
+norm or model.train().
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -12,6 +13,7 @@ ground truth of a call is packed into one pinned host mirror and shipped with on
 `assign_targets` is the same assignment kernel on its own, for DD3D.prepare_targets (the reference's call signature).
 """
 import ctypes as C
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -383,6 +385,77 @@ class TowerLayerGrads:
         return all(bool((t[n:] == fill).all()) for t, n in self._raw)
 
 
+class FpnConvGrads:
+    """Buffers and dd3d_fpn_grad_args of one FPN convolution per level (k x k, stride 1 or 2, a filter per level, no ReLU).
+
+    `in_hw`: per-level INPUT sizes; `x`: per level (mode, device address, pitch, plane scale) of the convolution's input, or None for a
+    call that only runs the input gradient; `g`: per-level NHWC gradient tensors at the convolution's output, pitch `g_pitch`; `w`:
+    per-level [Cout, k, k, Cin] filters; `scale`: per-level [Cout]; `mask`: per-level bindings like `x` of a stored tensor of the input's
+    shape, or None; `add`: per-level [B, h, w, Cin] tensors (entries may be None) or None; `pool`: per level None, a [B, 2h, 2w, Cin]
+    tensor, or "prev" for the input gradient of the level before (the transposed top-down path inside one call); `slab`: (part, qpart)
+    shared with other calls that run in stream order, or None to allocate them.  Outputs are allocated here, filled with `fill` and
+    followed by `guard` words of it."""
+    def __init__(self, device, B, in_hw, Cin, Cout, ksize, stride, x, g, g_pitch, w, scale, mask=None, add=None, pool=None, in_relu=False, slab=None,
+                 fill=0.0, guard=0, dgrad_rows=0, wgrad=True, dgrad=True):
+        L = len(in_hw)
+        self.B, self.in_hw, self.Cin, self.Cout, self.L, self.ksize, self.stride = B, list(in_hw), Cin, Cout, L, ksize, stride
+        self.out_hw = [((h + stride - 1) // stride, (w_ + stride - 1) // stride) for h, w_ in in_hw]
+        self.keep = (g, w, scale, add, pool, slab)
+        self.with_wgrad, self.with_dgrad = bool(wgrad), bool(dgrad)
+        a = hip.FpnGradArgs()
+        self._raw = []
+
+        def out(*shape):
+            numel = int(np.prod(shape))
+            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
+            self._raw.append((t, numel))
+            return t[:numel].view(*shape)
+
+        KK = ksize * ksize * Cin
+        self.n_slices = hip.fpn_grad_slices(B, in_hw, Cin, Cout, ksize, stride)
+        self.part = self.qpart = self.dw_level = self.dw = self.q = self.r = None
+        if wgrad:
+            if slab is None:
+                slab = (out(self.n_slices, Cout, KK), out(self.n_slices, Cout))
+            self.part, self.qpart = slab
+            assert self.part.numel() >= self.n_slices * Cout * KK and self.qpart.numel() >= self.n_slices * Cout
+            self.dw_level, self.dw = out(L, Cout, KK), out(L, Cout, KK)
+            self.q, self.r = out(L, Cout), out(L, Cout)
+            a.part, a.qpart, a.dw_level, a.dw = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw))
+            a.q, a.r = self.q.data_ptr(), self.r.data_ptr()
+        self.da = [out(B, h, w_, Cin) for h, w_ in in_hw] if dgrad else None
+        for l, (h, w_) in enumerate(in_hw):
+            a.x[l] = (x[l][1] or None) if x is not None else None
+            a.g[l], a.w[l], a.scale[l] = g[l].data_ptr(), w[l].data_ptr(), scale[l].data_ptr()
+            a.mask[l] = (mask[l][1] or None) if mask is not None and mask[l] is not None else None
+            a.add[l] = add[l].data_ptr() if add is not None and add[l] is not None else None
+            src = pool[l] if pool is not None else None
+            if isinstance(src, str):
+                assert src == "prev" and l > 0 and dgrad
+                src = self.da[l - 1]
+            a.pool[l] = src.data_ptr() if src is not None else None
+            a.pool_H[l], a.pool_W[l] = (int(src.shape[1]), int(src.shape[2])) if src is not None else (0, 0)
+            a.da[l] = self.da[l].data_ptr() if dgrad else None
+            a.H[l], a.W[l] = int(h), int(w_)
+        a.num_levels, a.B, a.Cin, a.Cout, a.g_pitch = L, int(B), int(Cin), int(Cout), int(g_pitch)
+        a.ksize, a.stride, a.in_relu = int(ksize), int(stride), int(bool(in_relu))
+        a.x_mode, a.x_pitch, a.x_plane_scale = (int(x[0][0]), int(x[0][2]), float(x[0][3])) if x is not None else (0, 0, 1.0)
+        m0 = next((m for m in (mask or []) if m is not None), None)
+        a.mask_mode, a.mask_pitch, a.mask_plane_scale = (int(m0[0]), int(m0[2]), float(m0[3])) if m0 is not None else (0, 0, 1.0)
+        assert x is None or all(v[0] == x[0][0] and v[2:] == x[0][2:] for v in x)
+        a.n_slices, a.dgrad_rows = self.n_slices, int(dgrad_rows)
+        self.args = a
+
+    def launch(self, lib, st):
+        if self.with_wgrad:
+            hip.check(lib.dd3d_fpn_wgrad(C.byref(self.args), st), "fpn_wgrad")
+        if self.with_dgrad:
+            hip.check(lib.dd3d_fpn_dgrad(C.byref(self.args), st), "fpn_dgrad")
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
 def norm_param_grads(conv, norm, scale, q, r):
     """Gradients of one level's share of a tower layer's per-channel parameters from the kernels' sums q = sum g and r = sum g * conv:
     {"norm.weight", "norm.bias", "bias"} as far as the modules have them as parameters.  The forward is layers.fold_norm's:
@@ -397,6 +470,99 @@ def norm_param_grads(conv, norm, scale, q, r):
     if b is not None:
         out["bias"] = scale.to(q.device) * q if norm is not None else q.clone()
     return out
+
+
+def _fpn_calls(fpn, acts):
+    """(ksize, stride, input sizes per level, Cin) of every weight-gradient call of the FPN backward."""
+    names, stages = list(fpn.in_features), list(fpn.stages)
+    calls = [(3, 1, [acts[f"t{s}"][1:3] for s in stages], acts[f"t{stages[0]}"][3])]
+    calls += [(1, 1, [acts[n][1:3]], acts[n][3]) for n in names]
+    if fpn.top_block is not None:
+        calls += [(3, 2, [acts[f"p{stages[-1] + i}"][1:3]], acts[f"p{stages[-1]}"][3]) for i in range(fpn.top_block.num_levels)]
+    return calls
+
+
+def fpn_slab_words(B, fpn, acts):
+    """Floats of (part, qpart) the largest weight-gradient call of the FPN backward needs."""
+    Cf = acts[f"t{fpn.stages[0]}"][3]
+    n = [(hip.fpn_grad_slices(B, hw, ci, Cf, k, s), k * k * ci) for k, s, hw, ci in _fpn_calls(fpn, acts)]
+    return max(sl * Cf * kk for sl, kk in n), max(sl * Cf for sl, _ in n)
+
+
+def fpn_backward(device, B, fpn, G, acts, vec, slab=None, fill=0.0, guard=0):
+    """The calls of the FPN backward in their order (include/dd3d_hip.h states the mathematics): the top block (P7, then P6) down to D
+    of the coarsest stage; the output convolutions (all weight gradients in one call, a filter per level; the input gradients finest
+    stage first, each adding the 2x2 sums of the finer stage's: the transposed top-down path); the laterals, coarsest stage first.
+
+    `G`: {p<s>: [B, h, w, Cf] gradient at every FPN output}; `acts`: {t<s> (stored top-down sum), p<s> (the coarsest stage's output and
+    p6), backbone feature name: ((mode, address, pitch, plane scale), H, W, C)} as stored; `vec`: host vector -> device.  Returns
+    ({key: FpnConvGrads}, {feature name: (gradient [B, h, w, C], real channels)}); a layer's `conv` is its module (`outputs`: a list)."""
+    from dd3d_amd.layers import fold_norm
+    if fpn._fuse_type != "sum":
+        raise NotImplementedError("FPN gradients implement FUSE_TYPE 'sum' (as the forward)")
+    names, stages = list(fpn.in_features), list(fpn.stages)  # finest first
+    Cf = acts[f"t{stages[0]}"][3]
+    layers, common = OrderedDict(), dict(slab=slab, fill=fill, guard=guard)
+
+    def filt(conv, cin):  # [Cout, k, k, cin]: the input channels padded with zero filters up to the buffer's width
+        w = conv.weight.detach().float()
+        if w.shape[1] < cin:
+            w = torch.cat([w, torch.zeros(w.shape[0], cin - w.shape[1], *w.shape[2:], dtype=w.dtype, device=w.device)], 1)
+        return w.permute(0, 2, 3, 1).contiguous().to(device)
+
+    scale_of = lambda conv: vec(fold_norm(conv, None)[0])
+    hw = lambda k: (acts[k][1], acts[k][2])
+    s5 = stages[-1]
+    D_top = G[f"p{s5}"]
+    if fpn.top_block is not None:
+        tb = fpn.top_block
+        D6 = G[f"p{s5 + 1}"]
+        if tb.num_levels == 2:  # P7 reads relu(p6): the stored p6, rectified while staged; the same stored p6 masks its input gradient
+            p6 = acts[f"p{s5 + 1}"][0]
+            lay = FpnConvGrads(device, B, [hw(f"p{s5 + 1}")], Cf, Cf, 3, 2, [p6], [G[f"p{s5 + 2}"]], Cf, [filt(tb.p7, Cf)], [scale_of(tb.p7)], mask=[p6],
+                               add=[D6], in_relu=True, **common)
+            lay.conv = tb.p7
+            layers["top_block.p7"] = lay
+            D6 = lay.da[0]
+        lay = FpnConvGrads(device, B, [hw(f"p{s5}")], Cf, Cf, 3, 2, [acts[f"p{s5}"][0]], [D6], Cf, [filt(tb.p6, Cf)], [scale_of(tb.p6)], add=[D_top],
+                           **common)
+        lay.conv = tb.p6
+        layers["top_block.p6"] = lay
+        D_top = lay.da[0]
+    D = [G[f"p{s}"] for s in stages[:-1]] + [D_top]
+    convs = [getattr(fpn, f"fpn_output{s}") for s in stages]
+    lay = FpnConvGrads(device, B, [hw(f"t{s}") for s in stages], Cf, Cf, 3, 1, [acts[f"t{s}"][0] for s in stages], D, Cf, [filt(c, Cf) for c in convs],
+                       [scale_of(c) for c in convs], pool=[None] + ["prev"] * (len(stages) - 1), **common)
+    lay.conv = convs
+    layers["outputs"] = lay
+    T = lay.da
+    backbone = OrderedDict()
+    for idx in reversed(range(len(stages))):
+        n, conv = names[idx], getattr(fpn, f"fpn_lateral{stages[idx]}")
+        cin = acts[n][3]
+        lay = FpnConvGrads(device, B, [hw(n)], cin, Cf, 1, 1, [acts[n][0]], [T[idx]], Cf, [filt(conv, cin)], [scale_of(conv)], **common)
+        lay.conv = conv
+        layers[f"lateral{stages[idx]}"] = lay
+        backbone[n] = (lay.da[0], int(conv.weight.shape[1]))
+    return layers, backbone
+
+
+def fpn_param_grads(named, layers):
+    """{parameter name: gradient of the parameter's shape} from the layers of `fpn_backward`; `named`: {id(parameter): name}.  The
+    gradients of the buffers' pad channels are dropped."""
+    params = {}
+    for lay in layers.values():
+        convs = lay.conv if isinstance(lay.conv, list) else [lay.conv]
+        for l, conv in enumerate(convs):
+            k, cin = lay.ksize, int(conv.weight.shape[1])
+            if id(conv.weight) in named:
+                params[named[id(conv.weight)]] = lay.dw[l].view(lay.Cout, k, k, lay.Cin)[..., :cin].permute(0, 3, 1, 2).contiguous()
+            norm = getattr(conv, "norm", None)
+            got = norm_param_grads(conv, norm, lay.keep[2][l], lay.q[l], lay.r[l])
+            for key, p in (("norm.weight", getattr(norm, "weight", None)), ("norm.bias", getattr(norm, "bias", None)), ("bias", conv.bias)):
+                if key in got and id(p) in named:
+                    params[named[id(p)]] = got[key]
+    return params
 
 
 def assemble_tower_grads(model, layers, feature_grads):
@@ -426,9 +592,11 @@ def assemble_tower_grads(model, layers, feature_grads):
 class LossPlan(ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
-    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False):
+    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
+                 fpn_grads=False):
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
-        self.keep_tower_outputs = bool(tower_grads)  # (`tower_grads` itself is the read-out method)
+        self.with_fpn_grads = bool(fpn_grads)  # (`fpn_grads` and `tower_grads` themselves are the read-out methods)
+        self.keep_tower_outputs = bool(tower_grads) or self.with_fpn_grads
         self.pred_grads = bool(pred_grads) or self.keep_tower_outputs
         self.grads = bool(grads) or self.pred_grads
         check_loss_config(model.cfg)
@@ -491,6 +659,8 @@ class LossPlan(ForwardPlan):
             self._pred_grads(model)
         if self.keep_tower_outputs:
             self._tower_grads(model)
+        if self.with_fpn_grads:
+            self._fpn_grads(model)
 
     def _loss_grads(self, a):
         """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
@@ -616,6 +786,56 @@ class LossPlan(ForwardPlan):
                 g, g_pitch = lay.da, Cin
             feature_da = g
         self.feature_grads = feature_da
+
+    def _fpn_grads(self, model):
+        """The FPN's backward behind the towers' (include/dd3d_hip.h states it; `fpn_backward` lays out the calls): the top block (P7,
+        then P6) down to D of the coarsest stage, the output convolutions, then the laterals -- on the main stream, still one hipGraph.
+        Every call shares one slab of weight-gradient partials with the towers', sized for the largest user."""
+        dev, B = self.device, self.B
+        fpn = model.backbone
+        names, stages = list(fpn.in_features), list(fpn.stages)  # finest first
+        view = lambda n: self.bufs[n].view()
+        selected = list(getattr(model, "in_features", None) or fpn._out_features)
+        Cf = view(f"p{stages[0]}").C
+        reads = [(n, self.bottom_up[n]) for n in names] + [(f"t{s}", view(f"fpn_lateral{s}")) for s in stages]
+        if fpn.top_block is not None:
+            reads += [(f"p{stages[-1] + i}", view(f"p{stages[-1] + i}")) for i in range(fpn.top_block.num_levels)]
+        acts = {k: (act_binding(self, v), v.H, v.W, v.C) for k, v in reads}
+        G = {}  # the gradient at every FPN output: the towers', or zeros for an output the heads do not read
+        for name in fpn._out_features:
+            v = view(name)
+            G[name] = self.feature_grads[selected.index(name)] if name in selected else torch.zeros((B, v.H, v.W, Cf), dtype=torch.float32, device=dev)
+            assert tuple(G[name].shape) == (B, v.H, v.W, Cf)
+        rows, qrows = fpn_slab_words(B, fpn, acts)
+        part, qpart = self.tower_slab
+        if part.numel() < rows or qpart.numel() < qrows:  # (the towers' calls take a prefix of the larger slab)
+            alloc = torch.empty if self.dry_run else torch.zeros
+            part = alloc(max(rows, part.numel()), dtype=torch.float32, device=dev)
+            qpart = alloc(max(qrows, qpart.numel()), dtype=torch.float32, device=dev)
+            for lay in self.tower_layers.values():
+                lay.part, lay.qpart = part, qpart
+                lay.args.part, lay.args.qpart = part.data_ptr(), qpart.data_ptr()
+            self.tower_slab = (part, qpart)
+        self.fpn_layers, self.backbone_grads = fpn_backward(dev, B, fpn, G, acts, self._vec, slab=self.tower_slab)
+        for key, lay in self.fpn_layers.items():
+            self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), "fpn_grads." + key, dict(kind="fpn_grads", layer=key)))
+        # Every tensor read above must still hold the forward's values when the backward runs.  PlanBase.buf gives every NAMED buffer a
+        # storage of its own for the life of the plan (there is no recycling allocator), so a tensor is intact as long as its name still
+        # maps to the buffer the view was taken from and no two of them share storage; nothing needs pinning beyond that.
+        self.fpn_reads, self.fpn_pinned = [v.buf.name for _, v in reads], []
+        for _, v in reads:
+            assert self.bufs.get(v.buf.name) is v.buf, f"the buffer {v.buf.name!r} the FPN backward reads was replaced"
+        if not self.dry_run:
+            addrs = [(v.pptr or v.ptr) for _, v in reads]
+            assert len(set(addrs)) == len(addrs), "two tensors the FPN backward reads share storage"
+
+    def fpn_grads(self):
+        """(backbone-feature gradients, FPN parameter gradients) of the last run, copies: {backbone_<name>: (B, C_name, h, w)} and {name in
+        model.named_parameters(): tensor of the parameter's shape}, float32; the gradients of the buffers' pad channels are dropped."""
+        if not self.with_fpn_grads:
+            raise RuntimeError("this LossPlan was built without fpn_grads=True")
+        feats = {f"backbone_{n}": d[..., :c].permute(0, 3, 1, 2).clone() for n, (d, c) in self.backbone_grads.items()}
+        return feats, fpn_param_grads({id(p): k for k, p in self.model.named_parameters()}, self.fpn_layers)
 
     def tower_grads(self):
         """(FPN-output gradients, tower parameter gradients) of the last run, copies: {feature<l>: (B, C, h_l, w_l)} and {name in

@@ -267,6 +267,36 @@ def tower_grad_slices(B, level_hw, Cin, Cout):
     return sum((u + ups - 1) // ups for u in units)
 
 
+FG_MAX_CIN, FG_MAX_COUT, FG_UNIT, FG_MIN_UNITS_PER_SLICE, FG_SLAB_BYTES, FG_MIN_TILES = 1024, 256, 64, 4, 160 << 20, 512
+
+
+class FpnGradArgs(C.Structure):
+    """`dd3d_fpn_grad_args`."""
+    _fields_ = [
+        ("x", C.c_void_p * MAX_LEVELS), ("g", C.c_void_p * MAX_LEVELS), ("w", C.c_void_p * MAX_LEVELS), ("scale", C.c_void_p * MAX_LEVELS),
+        ("mask", C.c_void_p * MAX_LEVELS), ("add", C.c_void_p * MAX_LEVELS), ("pool", C.c_void_p * MAX_LEVELS), ("da", C.c_void_p * MAX_LEVELS),
+        ("part", C.c_void_p), ("qpart", C.c_void_p), ("dw_level", C.c_void_p), ("dw", C.c_void_p), ("q", C.c_void_p), ("r", C.c_void_p),
+        ("H", C.c_int32 * MAX_LEVELS), ("W", C.c_int32 * MAX_LEVELS), ("pool_H", C.c_int32 * MAX_LEVELS), ("pool_W", C.c_int32 * MAX_LEVELS),
+        ("num_levels", C.c_int32), ("B", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("g_pitch", C.c_int32), ("ksize", C.c_int32),
+        ("stride", C.c_int32), ("in_relu", C.c_int32), ("x_mode", C.c_int32), ("x_pitch", C.c_int32), ("mask_mode", C.c_int32),
+        ("mask_pitch", C.c_int32), ("n_slices", C.c_int32), ("dgrad_rows", C.c_int32), ("x_plane_scale", C.c_float), ("mask_plane_scale", C.c_float)
+    ]
+
+
+def fpn_grad_slices(B, level_hw, Cin, Cout, ksize, stride):
+    """Rows of `part` / `qpart` one dd3d_fpn_wgrad call needs (the rule of dd3d_fpn_grad_slices, for plans built without a device):
+    the largest level's count.  `level_hw`: the INPUT sizes; a unit is 64 (stride 2: 32) output pixels of a row."""
+    unit = FG_UNIT // 2 if stride == 2 else FG_UNIT
+    max_slices = max(1, FG_SLAB_BYTES // (Cout * ksize * ksize * Cin * 4))
+    n = 0
+    for h, w in level_hw:
+        ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
+        units = B * ho * ((wo + unit - 1) // unit)
+        ups = max(FG_MIN_UNITS_PER_SLICE, (units + max_slices - 1) // max_slices)
+        n = max(n, (units + ups - 1) // ups)
+    return n
+
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
@@ -276,7 +306,8 @@ EXPORTS = [
     "dd3d_dense_depth_loss", "dd3d_dense_depth_loss_layout", "dd3d_loss_backward", "dd3d_loss_grad_layout",
     "dd3d_dense_depth_loss_backward", "dd3d_dense_depth_grad_rows", "dd3d_dense_depth_grad_layout",
     "dd3d_predictor_wgrad", "dd3d_predictor_dgrad", "dd3d_predictor_grad_slices", "dd3d_pred_grad_layout",
-    "dd3d_tower_wgrad", "dd3d_tower_dgrad", "dd3d_tower_grad_slices", "dd3d_tower_grad_layout"
+    "dd3d_tower_wgrad", "dd3d_tower_dgrad", "dd3d_tower_grad_slices", "dd3d_tower_grad_layout",
+    "dd3d_fpn_wgrad", "dd3d_fpn_dgrad", "dd3d_fpn_grad_slices", "dd3d_fpn_grad_layout"
 ]
 
 
@@ -365,6 +396,11 @@ def lib():
     L.dd3d_tower_grad_slices.argtypes = [C.POINTER(TowerGradArgs)]
     L.dd3d_tower_grad_slices.restype = C.c_int64
     L.dd3d_tower_grad_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_fpn_wgrad.argtypes = [C.POINTER(FpnGradArgs), C.c_void_p]
+    L.dd3d_fpn_dgrad.argtypes = [C.POINTER(FpnGradArgs), C.c_void_p]
+    L.dd3d_fpn_grad_slices.argtypes = [C.POINTER(FpnGradArgs)]
+    L.dd3d_fpn_grad_slices.restype = C.c_int64
+    L.dd3d_fpn_grad_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

@@ -119,17 +119,18 @@ class DD3D(nn.Module):
         self._evict_plans()
         return plan
 
-    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False):
+    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
         `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
         backward behind it as well (parameter and tower-output gradients; implies `grads`); `tower_grads`: the plan that goes on through
-        the head towers (their parameter gradients and the gradient at the FPN outputs; implies `pred_grads`)."""
+        the head towers (their parameter gradients and the gradient at the FPN outputs; implies `pred_grads`); `fpn_grads`: the plan that
+        goes on through the FPN (its parameter gradients and the gradient at the backbone's output features; implies `tower_grads`)."""
         from dd3d_amd.engine.losses import LossPlan
         key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + \
-            (("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
+            (("fpn_grads", ) if fpn_grads else ("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
         plan = self._plans.pop(key, None)
         if plan is None:
-            plan = LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
+            plan = LossPlan(self, B, Hp, Wp, fpn_grads=True) if fpn_grads else LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
                 LossPlan(self, B, Hp, Wp, grads=True) if grads else LossPlan(self, B, Hp, Wp)
             if self.use_graph:
                 plan.capture()
@@ -292,7 +293,7 @@ class DD3D(nn.Module):
 
     # ------------------------------------------------------------------ training losses (gradients: head maps and the predictor layer)
     @torch.no_grad()
-    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False):
+    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
@@ -306,12 +307,18 @@ class DD3D(nn.Module):
         Offset.bias) to float32 gradients of the parameter's shape.  With `tower_grads` the result has the same form and the backward
         goes on through the head towers: `grads` also holds the gradient at the FPN outputs the heads read (feature<l>: (B, 256, h_l,
         w_l)), `param_grads` also the tower parameters (every tower filter; a BN tower's per-level norm weight and bias; a norm-less
-        tower's conv bias; a FrozenBN tower's norm has no parameters).  The backward stops there: the FPN and the backbone have none,
-        and there is no optimiser, no batch-statistics norm and no model.train()."""
+        tower's conv bias; a FrozenBN tower's norm has no parameters).  With `fpn_grads` the result has the same form again and the
+        backward goes on through the FPN: everything `tower_grads` returns, bit for bit, and `grads` also holds the gradient at the
+        backbone's output features (backbone_<name>, e.g. backbone_level3 or backbone_stage2: (B, C_name, h, w)), `param_grads` also the
+        FPN's parameters (backbone.fpn_lateral<s>.weight, backbone.fpn_output<s>.weight, backbone.top_block.p6 / p7 weight and bias, and
+        whatever norm weights or conv biases FE.FPN.NORM owns).  The backward stops there: the backbone has none, and there is no
+        optimiser, no batch-statistics norm and no model.train()."""
         from dd3d_amd.engine import relax_arithmetic
         gt = [x["instances"] for x in batched_inputs]
         while True:
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), tower_grads=True) if tower_grads else \
+            tower_grads = tower_grads or fpn_grads
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), fpn_grads=True) if fpn_grads else \
+                self.get_loss_plan(*self.canvas_size(batched_inputs), tower_grads=True) if tower_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), pred_grads=True) if predictor_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), grads=True) if head_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs))
@@ -331,6 +338,9 @@ class DD3D(nn.Module):
                 if tower_grads:
                     feats, tparams = plan.tower_grads()
                     towers, params = dict(towers, **feats), dict(params, **tparams)
+                if fpn_grads:
+                    bfeats, fparams = plan.fpn_grads()
+                    towers, params = dict(towers, **bfeats), dict(params, **fparams)
                 return losses, dict(plan.head_grads(), **towers), params
             return (losses, plan.head_grads()) if head_grads else losses
 

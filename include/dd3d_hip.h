@@ -1,7 +1,7 @@
 /*
  * dd3d_hip.h -- C ABI of the MI355X (gfx950) DD3D forward-path library  (libdd3d_hip.so): the forward, the evaluators' kernels and the
  * training losses (detector: dd3d_loss_*, with the head-map gradients of dd3d_loss_backward and the predictor layer's backward below them,
- * dd3d_predictor_wgrad / dd3d_predictor_dgrad, and the head towers' below those, dd3d_tower_wgrad / dd3d_tower_dgrad; depth pre-training: dd3d_dense_depth_loss, with the gradient at the head's per-level maps
+ * dd3d_predictor_wgrad / dd3d_predictor_dgrad, and the head towers' below those, dd3d_tower_wgrad / dd3d_tower_dgrad, and the FPN's below those, dd3d_fpn_wgrad / dd3d_fpn_dgrad; depth pre-training: dd3d_dense_depth_loss, with the gradient at the head's per-level maps
  * of dd3d_dense_depth_loss_backward)
  *
  * The reference (TRI-ML/dd3d) has no FFI of its own for this path: it is pure Python and reaches
@@ -894,6 +894,84 @@ int dd3d_tower_wgrad(const dd3d_tower_grad_args* args, void* stream);
 int dd3d_tower_dgrad(const dd3d_tower_grad_args* args, void* stream);
 int64_t dd3d_tower_grad_slices(const dd3d_tower_grad_args* args);
 int dd3d_tower_grad_layout(int64_t* out, int32_t n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the FPN (csrc/fpn_grads.hip): detectron2's FPN.forward with LastLevelP6P7 (DLA-34) or LastLevelP6 (V2-99), fuse type
+ * "sum".  G_s: the gradient at the FPN output p_s (the towers' feature<l>; zero for an output DD3D.IN_FEATURES does not select); t_s: the
+ * STORED top-down sum of stage s; f_s: the backbone feature; (a, c): layers.fold_norm of a convolution, running statistics (a = 1,
+ * c = bias without a norm).
+ *   layer         forward                                    backward
+ *   P7            p7 = conv3x3s2(relu(p6); W7) + b7          dW7 = sum G7 (x) patches(relu(p6)), db7 = sum G7,
+ *                                                            D6 = G6 + [p6 > 0] * dgrad_s2(G7, W7)      (the mask from the STORED p6)
+ *   P6            p6 = conv3x3s2(p5; W6) + b6                dW6 = sum D6 (x) patches(p5), db6 = sum D6, D5 = G5 + dgrad_s2(D6, W6)
+ *   output conv   p_s = a_s * conv3x3(t_s; Wo_s) + c_s       dWo_s = a_s * sum D_s (x) patches(t_s), q_s = sum D_s, r_s = sum_k P * Wo_s
+ *   top-down sum  t_s = lat_s + up2(t_{s+1})                 finest stage: T_s = dgrad(a_s * D_s, Wo_s);
+ *                                                            others: T_s = dgrad(a_s * D_s, Wo_s) + pool2x2sum(T_{s-1})
+ *   lateral       lat_s = a'_s * (f_s . Wl_s) + c'_s         dWl_s = a'_s * sum T_s (x) f_s, q, r as above, dF_s = (a'_s * T_s) . Wl_s
+ * Without P7 D6 = G6; D_s = G_s except on the coarsest stage (D5 of the top-block chain).  P = the unscaled sum (dw_level), so that the
+ * norm read-out is the towers' (rstd * (r + (b_conv - mean) * q)).
+ *
+ * One call covers one convolution per level: k x k (ksize 1 or 3), stride 1 or 2, padding (k - 1) / 2, output size ceil(H / stride),
+ * a filter w[l] and a scale[l] per level.  H, W are the INPUT's sizes.  The levels run as separate launches in level order on the stream
+ * and share the slab: level l may read what level l - 1 wrote (pool[l] == da[l - 1]: the transposed top-down path in one call).
+ *   dw_level[l][n][ky][kx][c] = sum_{b,oy,ox} g_l[b,oy,ox,n] * X_l[b, oy s + ky - p, ox s + kx - p, c]     X = x, or max(x, 0) with in_relu
+ *   dw[l] = scale_l[n] * dw_level[l]       q[l][n] = sum g_l       r[l][n] = sum_k dw_level[l][n][k] * w_l[n][k]
+ *   da[l][b,y,x,c] = ((((M * sum_{n,ky,kx} scale_l[n] * g_l[b,(y+p-ky)/s,(x+p-kx)/s,n] * w_l[n][ky][kx][c]) + add) + t00) + t01) + t10) + t11
+ *     over the taps for which both divisions are exact; M = [mask_l[b,y,x,c] > 0] when mask[l] is set (a masked entry is an exact zero),
+ *     `+ add` when add[l] is set, and t_ij = pool[l][b, 2y + i, 2x + j, c] when pool[l] is set, added in exactly this order.
+ * Both are GEMMs on v_mfma_f32_32x32x2_f32 (exact f32 products, f32 accumulation): the weight gradient with K = the output pixels of a
+ * slice, per-slice partials summed in slice order by a second launch; the input gradient with one fresh accumulator per 32-channel chunk
+ * of Cout (its k k 32 terms in (tap, n) order), the chunks added in chunk order.  A zero g enters the input gradient as an exact zero
+ * whatever scale holds.  No float atomics, one writer and a fixed order per sum: two runs agree bit for bit, whichever tile is picked.
+ * Every word of dw_level, dw, q, r (wgrad) and da (dgrad) of the levels in use is written; nothing beyond them and the slab rows in use.
+ *
+ * x, mask: DD3D_PG_ACT_* storages (f32 NHWC with a pitch, or split planes of the slice's first chunk).  g: f32 NHWC, pitch g_pitch;
+ *   add, pool, da: f32 NHWC, pitch Cin.  part / qpart: dd3d_fpn_grad_slices(args) rows (host only; reads B, H, W, num_levels, Cin, Cout,
+ *   ksize, stride: the largest level's count -- units of 64 (stride 2: 32) output pixels of a row, DD3D_FG_MIN_UNITS_PER_SLICE per slice
+ *   at least, more once the slab would pass DD3D_FG_SLAB_BYTES).
+ * dd3d_fpn_wgrad: three launches per level (reads x, g, w, scale).  dd3d_fpn_dgrad: one launch per level (reads g, w, scale, mask, add,
+ *   pool).  Safe under stream capture.  dd3d_fpn_grad_layout: sizeof and field offsets.
+ * Rejected (-1, dd3d_last_error starts with the entry point's name): Cin not a multiple of 32 or above DD3D_FG_MAX_CIN, Cout not a
+ *   multiple of 32 or above DD3D_FG_MAX_COUT, ksize outside {1, 3}, stride outside {1, 2}, pitches not a multiple of 4 or too small,
+ *   unknown storages, null pointers, too few slab rows, a pool tensor that is not exactly twice the level's size, dgrad_rows outside
+ *   {0, 2, 4, 8}.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_FG_MAX_CIN 1024
+#define DD3D_FG_MAX_COUT 256
+#define DD3D_FG_UNIT 64
+#define DD3D_FG_MIN_UNITS_PER_SLICE 4
+#define DD3D_FG_SLAB_BYTES (160ll << 20)
+#define DD3D_FG_MIN_TILES 512
+typedef struct dd3d_fpn_grad_args {         /* host memory; every pointer is device memory */
+  const void* x[DD3D_MAX_LEVELS];           /* convolution input [B][H][W], storage x_mode */
+  const float* g[DD3D_MAX_LEVELS];          /* gradient at the convolution's output: [B][ceil(H/stride)][ceil(W/stride)][g_pitch] */
+  const float* w[DD3D_MAX_LEVELS];          /* [Cout][ksize][ksize][Cin] */
+  const float* scale[DD3D_MAX_LEVELS];      /* [Cout] */
+  const void* mask[DD3D_MAX_LEVELS];        /* stored tensor of the input's shape, storage mask_mode; or NULL */
+  const float* add[DD3D_MAX_LEVELS];        /* [B][H][W][Cin], or NULL */
+  const float* pool[DD3D_MAX_LEVELS];       /* [B][pool_H][pool_W][Cin] with pool_H == 2 H, pool_W == 2 W, or NULL */
+  float* da[DD3D_MAX_LEVELS];               /* [B][H][W][Cin] */
+  float* part;                              /* scratch [n_slices][Cout][ksize * ksize * Cin] */
+  float* qpart;                             /* scratch [n_slices][Cout] */
+  float* dw_level;                          /* [num_levels][Cout][ksize * ksize * Cin] */
+  float* dw;                                /* [num_levels][Cout][ksize * ksize * Cin] */
+  float* q;                                 /* [num_levels][Cout] */
+  float* r;                                 /* [num_levels][Cout] */
+  int32_t H[DD3D_MAX_LEVELS], W[DD3D_MAX_LEVELS];
+  int32_t pool_H[DD3D_MAX_LEVELS], pool_W[DD3D_MAX_LEVELS];
+  int32_t num_levels, B, Cin, Cout, g_pitch;
+  int32_t ksize, stride;
+  int32_t in_relu;                          /* weight gradient: rectify the staged input (P7 reads relu(p6)) */
+  int32_t x_mode, x_pitch;                  /* DD3D_PG_ACT_*; floats per pixel (DD3D_PG_ACT_F32) */
+  int32_t mask_mode, mask_pitch;
+  int32_t n_slices;                         /* rows of part / qpart */
+  int32_t dgrad_rows;                       /* rows of the input gradient's 16-pixel-wide tile: 2, 4, 8, or 0 = the call chooses */
+  float x_plane_scale, mask_plane_scale;    /* DD3D_PG_ACT_F16X2 */
+} dd3d_fpn_grad_args;
+int dd3d_fpn_wgrad(const dd3d_fpn_grad_args* args, void* stream);
+int dd3d_fpn_dgrad(const dd3d_fpn_grad_args* args, void* stream);
+int64_t dd3d_fpn_grad_slices(const dd3d_fpn_grad_args* args);
+int dd3d_fpn_grad_layout(int64_t* out, int32_t n);
 
 #ifdef __cplusplus
 }
