@@ -2,8 +2,9 @@
 the dict's weighted sum with respect to the head maps (csrc/loss_grads.hip) and, one layer further down, with respect to the predictor
 layer's parameters and the tower outputs it reads (csrc/predictor_grads.hip), and one layer further again through the head towers to
 their parameters and the FPN outputs (csrc/tower_grads.hip), and one stage further through the FPN to its parameters and the backbone's
-output features (csrc/fpn_grads.hip).  The backward stops there: the backbone has none, and there is no optimiser, batch-statistics
-norm or model.train().
+output features (csrc/fpn_grads.hip), and one stage further again through the DLA-34 backbone's level5 .. level2 to their parameters
+and the stem's output (csrc/backbone_grads.hip).  The backward stops there: the stem (base_layer, level0, level1) has none, and there
+is no optimiser, batch-statistics norm or model.train().
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -456,6 +457,274 @@ class FpnConvGrads:
         return all(bool((t[n:] == fill).all()) for t, n in self._raw)
 
 
+class BackboneConvGrads:
+    """Buffers and dd3d_backbone_grad_args of ONE backbone convolution (k x k, stride 1 or 2; csrc/backbone_grads.hip).
+
+    `H`, `W`: the INPUT's sizes; `x`, `y`: (mode, device address, pitch, plane scale) of the stored input and of the stored output whose
+    ReLU the gradient crosses (`y` None: no mask; `x` None for a call that only runs the input gradient); `g`: [B, Ho, Wo, Cout] f32
+    gradient at the output, possibly a channel slice of a wider tensor (its pitch is the tensor's stride); `w`: [Cout, k, k, Cin]; `scale`:
+    [Cout]; `add`: [B, H, W, Cin] (a slice may be given) or None; `res`: (gradient [B, H, W, Cin], binding of the stored tensor that masks
+    it) or None; `da`: a [B, H, W, Cin] slice of a wider gradient buffer to write into, or None to allocate it; `slab`: (part, qpart)
+    shared with other calls that run in stream order, or None to allocate them.  Outputs are allocated here, filled with `fill` and
+    followed by `guard` words of it."""
+    def __init__(self, device, B, H, W, Cin, Cout, ksize, stride, x, y, g, w, scale, add=None, res=None, da=None, slab=None, fill=0.0, guard=0,
+                 dgrad_rows=0, dgrad_group=0, wgrad=True, dgrad=True):
+        self.B, self.H, self.W, self.Cin, self.Cout, self.ksize, self.stride = B, int(H), int(W), Cin, Cout, ksize, stride
+        self.Ho, self.Wo = (self.H + stride - 1) // stride, (self.W + stride - 1) // stride
+        self.keep = (g, w, scale, add, res, slab)
+        self.scale = scale
+        self.with_wgrad, self.with_dgrad = bool(wgrad), bool(dgrad)
+        a = hip.BackboneGradArgs()
+        self._raw = []
+
+        def out(*shape):
+            numel = int(np.prod(shape))
+            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
+            self._raw.append((t, numel))
+            return t[:numel].view(*shape)
+
+        pitch = lambda t: int(t.stride(-2)) if t.shape[-2] > 1 or t.stride(-2) >= t.shape[-1] else int(t.shape[-1])
+        KK = ksize * ksize * Cin
+        assert tuple(g.shape) == (B, self.Ho, self.Wo, Cout) and g.stride(-1) == 1, (tuple(g.shape), (B, self.Ho, self.Wo, Cout))
+        self.n_slices = hip.backbone_grad_slices(B, self.H, self.W, Cin, Cout, ksize, stride)
+        self.part = self.qpart = self.dw_level = self.dw = self.q = self.r = None
+        if wgrad:
+            if slab is None:
+                slab = (out(self.n_slices, Cout, KK), out(self.n_slices, Cout))
+            self.part, self.qpart = slab
+            assert self.part.numel() >= self.n_slices * Cout * KK and self.qpart.numel() >= self.n_slices * Cout
+            self.dw_level, self.dw, self.q, self.r = out(Cout, KK), out(Cout, KK), out(Cout), out(Cout)
+            a.part, a.qpart, a.dw_level, a.dw = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw))
+            a.q, a.r = self.q.data_ptr(), self.r.data_ptr()
+        if dgrad:
+            self.da = out(B, self.H, self.W, Cin) if da is None else da
+            assert tuple(self.da.shape) == (B, self.H, self.W, Cin) and self.da.stride(-1) == 1
+            a.da, a.da_pitch = self.da.data_ptr(), pitch(self.da)
+        else:
+            self.da = None
+        a.x = (x[1] or None) if x is not None else None
+        a.y = (y[1] or None) if y is not None else None
+        self.masked = y is not None
+        a.g, a.w, a.scale, a.g_pitch = g.data_ptr(), w.data_ptr(), scale.data_ptr(), pitch(g)
+        if add is not None:
+            assert tuple(add.shape) == (B, self.H, self.W, Cin) and add.stride(-1) == 1
+            a.add, a.add_pitch = add.data_ptr(), pitch(add)
+        if res is not None:
+            rg, ry = res
+            assert tuple(rg.shape) == (B, self.H, self.W, Cin) and rg.stride(-1) == 1
+            a.res_g, a.res_pitch, a.res_y = rg.data_ptr(), pitch(rg), ry[1] or None
+            a.res_y_mode, a.res_y_pitch, a.res_y_plane_scale = int(ry[0]), int(ry[2]), float(ry[3])
+        else:
+            a.res_y_plane_scale = 1.0
+        a.B, a.H, a.W, a.Cin, a.Cout, a.ksize, a.stride = int(B), self.H, self.W, int(Cin), int(Cout), int(ksize), int(stride)
+        a.x_mode, a.x_pitch, a.x_plane_scale = (int(x[0]), int(x[2]), float(x[3])) if x is not None else (0, 0, 1.0)
+        a.y_mode, a.y_pitch, a.y_plane_scale = (int(y[0]), int(y[2]), float(y[3])) if y is not None else (0, 0, 1.0)
+        a.n_slices, a.dgrad_rows, a.dgrad_group = self.n_slices, int(dgrad_rows), int(dgrad_group)
+        self.args = a
+
+    def launch(self, lib, st):
+        if self.with_wgrad:
+            hip.check(lib.dd3d_backbone_wgrad(C.byref(self.args), st), "backbone_wgrad")
+        if self.with_dgrad:
+            hip.check(lib.dd3d_backbone_dgrad(C.byref(self.args), st), "backbone_dgrad")
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
+class PoolGrads:
+    """Buffers and dd3d_pool_grad_args of one 2x2 max-pool backward: `x` the binding of the pool's stored input ([B, H, W, C]), `g` the
+    gradient at the pooled tensor (None with `res` alone), `res`: (a second part of it, binding of the stored tensor that masks it) or
+    None, `add` [B, H, W, C] or None.  `da` is allocated here (filled with `fill`, followed by `guard` words)."""
+    def __init__(self, device, B, H, W, Cc, x, g, add=None, res=None, fill=0.0, guard=0):
+        self.B, self.H, self.W, self.C = B, int(H), int(W), int(Cc)
+        self.keep = (g, add, res)
+        numel = B * self.H * self.W * self.C
+        t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
+        self._raw = [(t, numel)]
+        self.da = t[:numel].view(B, self.H, self.W, self.C)
+        pitch = lambda v: int(v.stride(-2)) if v.shape[-2] > 1 or v.stride(-2) >= v.shape[-1] else int(v.shape[-1])
+        a = hip.PoolGradArgs()
+        a.x, a.da, a.res_y_plane_scale = x[1] or None, self.da.data_ptr(), 1.0
+        for t in ([g] if g is not None else []) + ([res[0]] if res is not None else []):
+            assert tuple(t.shape) == (B, self.H // 2, self.W // 2, self.C) and t.stride(-1) == 1
+        if g is not None:
+            a.g, a.g_pitch = g.data_ptr(), pitch(g)
+        if res is not None:
+            a.res_g, a.res_pitch, a.res_y = res[0].data_ptr(), pitch(res[0]), res[1][1] or None
+            a.res_y_mode, a.res_y_pitch, a.res_y_plane_scale = int(res[1][0]), int(res[1][2]), float(res[1][3])
+        a.B, a.H, a.W, a.C = int(B), self.H, self.W, self.C
+        a.x_mode, a.x_pitch, a.x_plane_scale = int(x[0]), int(x[2]), float(x[3])
+        a.da_pitch = self.C
+        if add is not None:
+            assert tuple(add.shape) == (B, self.H, self.W, self.C) and add.stride(-1) == 1
+            a.add, a.add_pitch = add.data_ptr(), pitch(add)
+        self.args = a
+
+    def launch(self, lib, st):
+        hip.check(lib.dd3d_maxpool2x2_backward(C.byref(self.args), st), "maxpool2x2_backward")
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
+def slice_binding(bind, c0, npix):
+    """The binding (mode, address, pitch, plane scale) of the channel slice that starts at channel `c0` of a stored buffer with `npix`
+    pixels: f32 moves the pointer by channels, split planes by whole 32-channel chunk images (f16x2: 128, bf16x3: 192 bytes a pixel)."""
+    mode, addr, pitch, scale = bind
+    if not addr or not c0:
+        return bind
+    if mode == hip.PG_ACT_F32:
+        return (mode, addr + 4 * c0, pitch, scale)
+    assert c0 % 32 == 0, c0
+    return (mode, addr + (c0 // 32) * npix * (128 if mode == hip.PG_ACT_F16X2 else 192), pitch, scale)
+
+
+def check_dla_backward(dla, model=None):
+    """NotImplementedError naming what the backbone backward does not cover (it covers BackboneLowering._tree: DLA-34)."""
+    from dd3d_amd.modeling.dla import DLA, BasicBlock
+    if not isinstance(dla, DLA):
+        raise NotImplementedError(f"backbone gradients cover the DLA-34 backbone; {type(dla).__name__} (the V2-99 family) has no backward")
+    if dla.block is not BasicBlock:
+        raise NotImplementedError(f"backbone gradients cover BasicBlock trees (DLA-34); the {dla.block.__name__} DLA variants have no backward")
+    if max(dla.levels) > 2 or dla.residual_root:
+        raise NotImplementedError("backbone gradients cover trees at most two deep without a residual root (DLA-34)")
+    if model is not None and getattr(model, "force_generic_dla", False):
+        raise NotImplementedError("backbone gradients follow the DLA-34 lowering; force_generic_dla has no backward")
+
+
+def _dla_tree_calls(m, H, W):
+    """(ksize, stride, input H, W, Cin, Cout) of every convolution of a tree whose input is H x W."""
+    s = m.stride
+    Ho, Wo = H // s, W // s
+    if m.levels == 2:
+        return _dla_tree_calls(m.tree1, H, W) + _dla_tree_calls(m.tree2, Ho, Wo)
+    oc, ic = m.out_channels, m.in_channels
+    calls = [(1, 1, Ho, Wo, m.root_dim, oc), (3, 1, Ho, Wo, oc, oc), (3, 1, Ho, Wo, oc, oc), (3, 1, Ho, Wo, oc, oc), (3, s, H, W, ic, oc)]
+    if m.project is not None:
+        calls.append((1, 1, Ho, Wo, ic, oc))
+    return calls
+
+
+def dla_slab_words(B, dla, H1, W1):
+    """Floats of (part, qpart) the largest weight-gradient call of the backbone backward needs; H1 x W1: the level1 tensor."""
+    rows = qrows = 0
+    H, W = H1, W1
+    for lvl in range(2, 6):
+        tree = getattr(dla, f"level{lvl}")
+        for k, s, h, w_, ci, co in _dla_tree_calls(tree, H, W):
+            n = hip.backbone_grad_slices(B, h, w_, ci, co, k, s)
+            rows, qrows = max(rows, n * co * k * k * ci), max(qrows, n * co)
+        H, W = H // 2, W // 2
+    return rows, qrows
+
+
+def dla_backward(device, B, dla, G, acts, vec, slab=None, fill=0.0, guard=0):
+    """The calls of the DLA-34 backward in their order, level5 down to level2 (include/dd3d_hip.h states the mathematics).  Per depth-1
+    tree: root, tree2.conv2, tree2.conv1, tree1.conv2, project, tree1.conv1, pool; a depth-2 tree runs its tree2 first, then its tree1.
+
+    `G`: {level<n>: [B, h, w, C] gradient the FPN sends to a backbone output feature}; level5's is required; `acts`: {name of a stored
+    buffer of BackboneLowering._tree (<tree>.cat, <tree>.tree1.mid, <tree>.tree2.mid, <tree>.bottom, <tree>.out) and "level1" for the
+    tensor level2 reads: ((mode, address, pitch, plane scale) of the WHOLE buffer, H, W, C)}; `vec`: host vector -> device.  Returns
+    ({key: BackboneConvGrads or PoolGrads}, the gradient [B, h1, w1, C1] at the level1 tensor); a convolution's layer carries its module
+    as `conv` and what it reads as `src` = {operand: (buffer name, first channel, channels)}."""
+    from dd3d_amd.layers import fold_norm
+    check_dla_backward(dla)
+    layers, common = OrderedDict(), dict(fill=fill, guard=guard)
+
+    def bind(ref):
+        key, c0, _ = ref
+        b, h, w_, _ = acts[key]
+        return slice_binding(b, c0, B * h * w_)
+
+    def conv(key, mod, x, y, g, stride, add=None, res=None):
+        k, cin, cout = int(mod.weight.shape[-1]), int(mod.weight.shape[1]), int(mod.weight.shape[0])
+        assert x[2] == cin and (y is None or y[2] == cout), (key, x, y)
+        H, W = acts[x[0]][1], acts[x[0]][2]
+        w = mod.weight.detach().float().permute(0, 2, 3, 1).contiguous().to(device)
+        lay = BackboneConvGrads(device, B, H, W, cin, cout, k, stride, bind(x), bind(y) if y is not None else None, g, w, vec(fold_norm(mod, None)[0]),
+                                add=add, res=(res[0], bind(res[1])) if res is not None else None, slab=slab, **common)
+        lay.conv, lay.src = mod, dict(x=x, y=y, res_y=res[1] if res is not None else None)
+        layers[key] = lay
+        return lay.da
+
+    def tree1(m, name, x, dst, G_out, cat=None, bottom=None, bottom_add=None, x_add=None, x_slice=None):
+        """A depth-1 tree: returns (the gradient at its input, the gradient over its root's concat buffer)."""
+        oc, ic, s = m.out_channels, m.in_channels, m.stride
+        own = cat is None
+        cat = cat or name + ".cat"
+        dst = dst or (name + ".out", 0, oc)
+        Dcat = conv(name + ".root", m.root.conv, (cat, 0, acts[cat][3]), dst, G_out, 1)
+        x2, x1, mid1, mid2 = (cat, 0, oc), (cat, oc, oc), (name + ".tree1.mid", 0, oc), (name + ".tree2.mid", 0, oc)
+        if own and m.level_root:
+            bottom, bottom_add = (cat, 2 * oc, ic), Dcat[..., 2 * oc:2 * oc + ic]
+        D2, D1 = Dcat[..., :oc], Dcat[..., oc:2 * oc]
+        Gmid2 = conv(name + ".tree2.conv2", m.tree2.conv2, mid2, x2, D2, 1)
+        Gx1 = conv(name + ".tree2.conv1", m.tree2.conv1, x1, mid2, Gmid2, 1, add=D1, res=(D2, x2))
+        Gmid1 = conv(name + ".tree1.conv2", m.tree1.conv2, mid1, x1, Gx1, 1)
+        if s == 2:
+            Gbottom, res = bottom_add, None
+            if m.project is not None:  # (the gradient at `residual` is Gx1 * [x1 > 0]: the call masks it by the stored x1)
+                Gbottom = conv(name + ".project", m.project, bottom or (name + ".bottom", 0, ic), x1, Gx1, 1, add=bottom_add)
+            else:  # the pooled tensor is the residual itself
+                res = (Gx1, bind(x1))
+            Cx = conv(name + ".tree1.conv1", m.tree1.conv1, x, mid1, Gmid1, 2, add=x_add)
+            H, W = acts[x[0]][1], acts[x[0]][2]
+            pool = PoolGrads(device, B, H, W, ic, bind(x), Gbottom, add=Cx, res=res, **common)
+            pool.src = dict(x=x, res_y=x1 if res is not None else None)
+            layers[name + ".pool"] = pool
+            return pool.da, Dcat
+        assert x_add is None or x_slice is None, name
+        A = Dcat[..., x_slice[0]:x_slice[0] + x_slice[1]] if x_slice is not None else x_add
+        if m.project is not None:  # bottom = x: the project's input gradient joins x's
+            A = conv(name + ".project", m.project, x, x1, Gx1, 1, add=A)
+            return conv(name + ".tree1.conv1", m.tree1.conv1, x, mid1, Gmid1, 1, add=A), Dcat
+        return conv(name + ".tree1.conv1", m.tree1.conv1, x, mid1, Gmid1, 1, add=A, res=(Gx1, x1)), Dcat
+
+    def tree(m, name, x, G_out, x_add):
+        if m.levels == 1:
+            return tree1(m, name, x, None, G_out, x_add=x_add)[0]
+        oc, ic = m.out_channels, m.in_channels
+        cat2 = name + ".cat"
+        off, bottom = 2 * oc, None
+        if m.level_root:
+            bottom, off = (cat2, off, ic), off + ic
+        t1 = (cat2, off, oc)
+        G_t1, Dcat2 = tree1(m.tree2, name + ".tree2", t1, None, G_out, cat=cat2, x_slice=(off, oc))
+        return tree1(m.tree1, name + ".tree1", x, t1, G_t1, bottom=bottom, bottom_add=Dcat2[..., 2 * oc:2 * oc + ic] if m.level_root else None,
+                     x_add=x_add)[0]
+
+    out_name = lambda lvl: f"level{lvl}"
+    g = G["level5"]
+    for lvl in (5, 4, 3, 2):
+        m = getattr(dla, f"level{lvl}")
+        if lvl == 2:
+            x = ("level1", 0, m.in_channels)
+        else:
+            p = getattr(dla, f"level{lvl - 1}")
+            x = (f"level{lvl - 1}.out" if p.levels == 1 else f"level{lvl - 1}.tree2.out", 0, m.in_channels)
+        g = tree(m, out_name(lvl), x, g, G.get(f"level{lvl - 1}"))
+    return layers, g
+
+
+def dla_param_grads(named, layers, prefix=""):
+    """{parameter name: gradient of the parameter's shape} from the layers of `dla_backward`; `named`: {id(parameter): name}."""
+    params = {}
+    for lay in layers.values():
+        conv = getattr(lay, "conv", None)
+        if conv is None:
+            continue
+        k, cin = lay.ksize, int(conv.weight.shape[1])
+        if id(conv.weight) in named:
+            params[named[id(conv.weight)]] = lay.dw.view(lay.Cout, k, k, lay.Cin)[..., :cin].permute(0, 3, 1, 2).contiguous()
+        norm = getattr(conv, "norm", None)
+        got = norm_param_grads(conv, norm, lay.scale, lay.q, lay.r)
+        for key, p in (("norm.weight", getattr(norm, "weight", None)), ("norm.bias", getattr(norm, "bias", None)), ("bias", conv.bias)):
+            if key in got and id(p) in named:
+                params[named[id(p)]] = got[key]
+    return params
+
+
 def norm_param_grads(conv, norm, scale, q, r):
     """Gradients of one level's share of a tower layer's per-channel parameters from the kernels' sums q = sum g and r = sum g * conv:
     {"norm.weight", "norm.bias", "bias"} as far as the modules have them as parameters.  The forward is layers.fold_norm's:
@@ -593,9 +862,12 @@ class LossPlan(ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
     def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
-                 fpn_grads=False):
+                 fpn_grads=False, backbone_grads=False):
+        self.with_backbone_grads = bool(backbone_grads)  # (`backbone_grads`, `fpn_grads` and `tower_grads` themselves are the read-out methods)
+        if self.with_backbone_grads:  # before anything is built or launched
+            check_dla_backward(model.backbone.bottom_up, model)
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
-        self.with_fpn_grads = bool(fpn_grads)  # (`fpn_grads` and `tower_grads` themselves are the read-out methods)
+        self.with_fpn_grads = bool(fpn_grads) or self.with_backbone_grads
         self.keep_tower_outputs = bool(tower_grads) or self.with_fpn_grads
         self.pred_grads = bool(pred_grads) or self.keep_tower_outputs
         self.grads = bool(grads) or self.pred_grads
@@ -661,6 +933,8 @@ class LossPlan(ForwardPlan):
             self._tower_grads(model)
         if self.with_fpn_grads:
             self._fpn_grads(model)
+        if self.with_backbone_grads:
+            self._backbone_grads(model)
 
     def _loss_grads(self, a):
         """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
@@ -816,7 +1090,7 @@ class LossPlan(ForwardPlan):
                 lay.part, lay.qpart = part, qpart
                 lay.args.part, lay.args.qpart = part.data_ptr(), qpart.data_ptr()
             self.tower_slab = (part, qpart)
-        self.fpn_layers, self.backbone_grads = fpn_backward(dev, B, fpn, G, acts, self._vec, slab=self.tower_slab)
+        self.fpn_layers, self.backbone_feature_grads = fpn_backward(dev, B, fpn, G, acts, self._vec, slab=self.tower_slab)
         for key, lay in self.fpn_layers.items():
             self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), "fpn_grads." + key, dict(kind="fpn_grads", layer=key)))
         # Every tensor read above must still hold the forward's values when the backward runs.  PlanBase.buf gives every NAMED buffer a
@@ -834,8 +1108,65 @@ class LossPlan(ForwardPlan):
         model.named_parameters(): tensor of the parameter's shape}, float32; the gradients of the buffers' pad channels are dropped."""
         if not self.with_fpn_grads:
             raise RuntimeError("this LossPlan was built without fpn_grads=True")
-        feats = {f"backbone_{n}": d[..., :c].permute(0, 3, 1, 2).clone() for n, (d, c) in self.backbone_grads.items()}
+        feats = {f"backbone_{n}": d[..., :c].permute(0, 3, 1, 2).clone() for n, (d, c) in self.backbone_feature_grads.items()}
         return feats, fpn_param_grads({id(p): k for k, p in self.model.named_parameters()}, self.fpn_layers)
+
+    def _backbone_grads(self, model):
+        """The DLA-34 backbone's backward behind the FPN's (include/dd3d_hip.h states it; `dla_backward` lays out the calls): level5 down
+        to level2, one weight-gradient and one input-gradient call per convolution and one launch per 2x2 max-pool, on the main stream --
+        still one hipGraph.  The stem (base_layer, level0, level1) stays frozen: the chain ends at the gradient of the tensor level2
+        reads.  Every call shares the one slab of weight-gradient partials, sized for its largest user."""
+        dev, B = self.device, self.B
+        dla = model.backbone.bottom_up
+        l1 = self.bufs[f"level1.{len(dla.level1) - 1}"].view()  # the stem's output, fused or launch by launch
+        views = {"level1": l1}
+        for name, b in self.bufs.items():
+            if name.split(".")[0] in ("level2", "level3", "level4", "level5") and name.rsplit(".", 1)[-1] in ("cat", "mid", "bottom", "out"):
+                views[name] = b.view()
+        acts = {k: (act_binding(self, v), v.H, v.W, v.C) for k, v in views.items()}
+        G = {}
+        for n, (d, c) in self.backbone_feature_grads.items():
+            assert c == d.shape[-1], (n, c, tuple(d.shape))
+            G[n] = d
+        rows, qrows = dla_slab_words(B, dla, l1.H, l1.W)
+        part, qpart = self.tower_slab
+        # the whole slab, whoever sizes it: a call's slices stay within DD3D_TG_SLAB_BYTES; the towers' rule rounds up once per pyramid
+        # level (dd3d_tower_grad_slices: "+ at most one row per level"), so their prefix may pass it by that many tower slices
+        slack = 4 * len(self.features) * max(lay.Cout * 9 * lay.Cin for lay in self.tower_layers.values())
+        assert 4 * rows <= hip.TG_SLAB_BYTES and 4 * max(rows, part.numel()) <= hip.TG_SLAB_BYTES + slack, \
+            f"the backward's slab ({4 * max(rows, part.numel())} bytes) exceeds DD3D_TG_SLAB_BYTES"
+        if part.numel() < rows or qpart.numel() < qrows:  # (the towers' and the FPN's calls take a prefix of the larger slab)
+            alloc = torch.empty if self.dry_run else torch.zeros
+            part = alloc(max(rows, part.numel()), dtype=torch.float32, device=dev)
+            qpart = alloc(max(qrows, qpart.numel()), dtype=torch.float32, device=dev)
+            for lay in list(self.tower_layers.values()) + [l for l in self.fpn_layers.values() if l.with_wgrad]:
+                lay.part, lay.qpart = part, qpart
+                lay.args.part, lay.args.qpart = part.data_ptr(), qpart.data_ptr()
+            self.tower_slab = (part, qpart)
+        self.backbone_layers, self.level1_grad = dla_backward(dev, B, dla, G, acts, self._vec, slab=self.tower_slab)
+        for key, lay in self.backbone_layers.items():
+            self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), "backbone_grads." + key, dict(kind="backbone_grads", layer=key)))
+        # as for the FPN: every stored tensor read above must still hold the forward's values when the backward runs
+        used = []
+        for lay in self.backbone_layers.values():
+            for ref in lay.src.values():
+                if ref is not None and ref[0] not in used:
+                    used.append(ref[0])
+        self.backbone_reads = [views[k].buf.name for k in used]
+        for k in used:
+            assert self.bufs.get(views[k].buf.name) is views[k].buf, f"the buffer {views[k].buf.name!r} the backbone backward reads was replaced"
+        if not self.dry_run:
+            addrs = [(views[k].pptr or views[k].ptr) for k in used]
+            assert len(set(addrs)) == len(addrs), "two tensors the backbone backward reads share storage"
+
+    def backbone_grads(self):
+        """(the gradient at the stem's stored output, backbone parameter gradients) of the last run, copies: {backbone_level1: (B, C1,
+        Hp / 2, Wp / 2)} -- not yet masked by that tensor's own ReLU -- and {name in model.named_parameters(): tensor of the parameter's
+        shape} for every parameter of backbone.bottom_up.level2 .. level5, float32."""
+        if not self.with_backbone_grads:
+            raise RuntimeError("this LossPlan was built without backbone_grads=True")
+        named = {id(p): k for k, p in self.model.named_parameters()}
+        return {"backbone_level1": self.level1_grad.permute(0, 3, 1, 2).clone()}, dla_param_grads(named, self.backbone_layers)
 
     def tower_grads(self):
         """(FPN-output gradients, tower parameter gradients) of the last run, copies: {feature<l>: (B, C, h_l, w_l)} and {name in

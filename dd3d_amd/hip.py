@@ -297,6 +297,43 @@ def fpn_grad_slices(B, level_hw, Cin, Cout, ksize, stride):
     return n
 
 
+BG_MAX_CIN, BG_MAX_COUT, BG_UNIT, BG_MIN_UNITS_PER_SLICE, BG_MIN_TILES, BG_MAX_PIXELS = 1280, 512, 64, 4, 512, 1 << 26
+
+
+class BackboneGradArgs(C.Structure):
+    """`dd3d_backbone_grad_args`."""
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("g", C.c_void_p), ("w", C.c_void_p), ("scale", C.c_void_p), ("add", C.c_void_p),
+        ("res_g", C.c_void_p), ("res_y", C.c_void_p), ("da", C.c_void_p), ("part", C.c_void_p), ("qpart", C.c_void_p), ("dw_level", C.c_void_p),
+        ("dw", C.c_void_p), ("q", C.c_void_p), ("r", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32),
+        ("Cout", C.c_int32), ("ksize", C.c_int32), ("stride", C.c_int32), ("g_pitch", C.c_int32), ("add_pitch", C.c_int32),
+        ("res_pitch", C.c_int32), ("da_pitch", C.c_int32), ("x_mode", C.c_int32), ("x_pitch", C.c_int32), ("y_mode", C.c_int32),
+        ("y_pitch", C.c_int32), ("res_y_mode", C.c_int32), ("res_y_pitch", C.c_int32), ("n_slices", C.c_int32), ("dgrad_rows", C.c_int32),
+        ("dgrad_group", C.c_int32), ("x_plane_scale", C.c_float), ("y_plane_scale", C.c_float), ("res_y_plane_scale", C.c_float)
+    ]
+
+
+class PoolGradArgs(C.Structure):
+    """`dd3d_pool_grad_args`."""
+    _fields_ = [
+        ("x", C.c_void_p), ("g", C.c_void_p), ("res_g", C.c_void_p), ("res_y", C.c_void_p), ("add", C.c_void_p), ("da", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("x_mode", C.c_int32), ("x_pitch", C.c_int32),
+        ("res_y_mode", C.c_int32), ("res_y_pitch", C.c_int32), ("g_pitch", C.c_int32), ("res_pitch", C.c_int32), ("add_pitch", C.c_int32),
+        ("da_pitch", C.c_int32), ("x_plane_scale", C.c_float), ("res_y_plane_scale", C.c_float)
+    ]
+
+
+def backbone_grad_slices(B, H, W, Cin, Cout, ksize, stride):
+    """Rows of `part` / `qpart` one dd3d_backbone_wgrad call needs (the rule of dd3d_backbone_grad_slices, for plans built without a
+    device).  H, W: the INPUT's sizes; a unit is 64 (stride 2: 32) output pixels of a row; the slab stays within TG_SLAB_BYTES."""
+    unit = BG_UNIT // 2 if stride == 2 else BG_UNIT
+    max_slices = max(1, TG_SLAB_BYTES // (Cout * ksize * ksize * Cin * 4))
+    ho, wo = (H + stride - 1) // stride, (W + stride - 1) // stride
+    units = B * ho * ((wo + unit - 1) // unit)
+    ups = max(BG_MIN_UNITS_PER_SLICE, (units + max_slices - 1) // max_slices)
+    return (units + ups - 1) // ups
+
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
@@ -307,7 +344,8 @@ EXPORTS = [
     "dd3d_dense_depth_loss_backward", "dd3d_dense_depth_grad_rows", "dd3d_dense_depth_grad_layout",
     "dd3d_predictor_wgrad", "dd3d_predictor_dgrad", "dd3d_predictor_grad_slices", "dd3d_pred_grad_layout",
     "dd3d_tower_wgrad", "dd3d_tower_dgrad", "dd3d_tower_grad_slices", "dd3d_tower_grad_layout",
-    "dd3d_fpn_wgrad", "dd3d_fpn_dgrad", "dd3d_fpn_grad_slices", "dd3d_fpn_grad_layout"
+    "dd3d_fpn_wgrad", "dd3d_fpn_dgrad", "dd3d_fpn_grad_slices", "dd3d_fpn_grad_layout",
+    "dd3d_backbone_wgrad", "dd3d_backbone_dgrad", "dd3d_backbone_grad_slices", "dd3d_maxpool2x2_backward", "dd3d_backbone_grad_layout"
 ]
 
 
@@ -401,6 +439,12 @@ def lib():
     L.dd3d_fpn_grad_slices.argtypes = [C.POINTER(FpnGradArgs)]
     L.dd3d_fpn_grad_slices.restype = C.c_int64
     L.dd3d_fpn_grad_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_backbone_wgrad.argtypes = [C.POINTER(BackboneGradArgs), C.c_void_p]
+    L.dd3d_backbone_dgrad.argtypes = [C.POINTER(BackboneGradArgs), C.c_void_p]
+    L.dd3d_backbone_grad_slices.argtypes = [C.POINTER(BackboneGradArgs)]
+    L.dd3d_backbone_grad_slices.restype = C.c_int64
+    L.dd3d_maxpool2x2_backward.argtypes = [C.POINTER(PoolGradArgs), C.c_void_p]
+    L.dd3d_backbone_grad_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

@@ -119,18 +119,20 @@ class DD3D(nn.Module):
         self._evict_plans()
         return plan
 
-    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False):
+    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
         `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
         backward behind it as well (parameter and tower-output gradients; implies `grads`); `tower_grads`: the plan that goes on through
         the head towers (their parameter gradients and the gradient at the FPN outputs; implies `pred_grads`); `fpn_grads`: the plan that
-        goes on through the FPN (its parameter gradients and the gradient at the backbone's output features; implies `tower_grads`)."""
+        goes on through the FPN (its parameter gradients and the gradient at the backbone's output features; implies `tower_grads`);
+        `backbone_grads`: the plan that goes on through DLA-34's level5 .. level2 (their parameter gradients and the gradient at the stem's
+        output; implies `fpn_grads`)."""
         from dd3d_amd.engine.losses import LossPlan
         key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + \
-            (("fpn_grads", ) if fpn_grads else ("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
+            (("backbone_grads", ) if backbone_grads else ("fpn_grads", ) if fpn_grads else ("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
         plan = self._plans.pop(key, None)
         if plan is None:
-            plan = LossPlan(self, B, Hp, Wp, fpn_grads=True) if fpn_grads else LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
+            plan = LossPlan(self, B, Hp, Wp, backbone_grads=True) if backbone_grads else LossPlan(self, B, Hp, Wp, fpn_grads=True) if fpn_grads else LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
                 LossPlan(self, B, Hp, Wp, grads=True) if grads else LossPlan(self, B, Hp, Wp)
             if self.use_graph:
                 plan.capture()
@@ -293,7 +295,7 @@ class DD3D(nn.Module):
 
     # ------------------------------------------------------------------ training losses (gradients: head maps and the predictor layer)
     @torch.no_grad()
-    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False):
+    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
@@ -311,13 +313,21 @@ class DD3D(nn.Module):
         backward goes on through the FPN: everything `tower_grads` returns, bit for bit, and `grads` also holds the gradient at the
         backbone's output features (backbone_<name>, e.g. backbone_level3 or backbone_stage2: (B, C_name, h, w)), `param_grads` also the
         FPN's parameters (backbone.fpn_lateral<s>.weight, backbone.fpn_output<s>.weight, backbone.top_block.p6 / p7 weight and bias, and
-        whatever norm weights or conv biases FE.FPN.NORM owns).  The backward stops there: the backbone has none, and there is no
-        optimiser, no batch-statistics norm and no model.train()."""
+        whatever norm weights or conv biases FE.FPN.NORM owns).  With `backbone_grads` the result has the same form once more and the
+        backward goes on through the DLA-34 backbone, level5 down to level2: everything `fpn_grads` returns, bit for bit (backbone_level3..5
+        stay the FPN's contribution at those features), `grads` also holds backbone_level1 -- the gradient at the stem's stored output,
+        (B, 32, Hp / 2, Wp / 2), not yet masked by that tensor's own ReLU -- and `param_grads` also every parameter of
+        backbone.bottom_up.level2 .. level5 (the filters of tree*.conv1 / conv2, project and root.conv; a BN backbone's norm weights and
+        biases; a norm-less backbone's conv biases; FrozenBN, the released configs' norm, owns nothing).  The backward stops there: the
+        stem (base_layer, level0, level1) has none, and there is no optimiser, no batch-statistics norm and no model.train().  V2-99, the
+        Bottleneck DLA variants, force_generic_dla and the reduced arithmetic modes raise NotImplementedError."""
         from dd3d_amd.engine import relax_arithmetic
         gt = [x["instances"] for x in batched_inputs]
         while True:
+            fpn_grads = fpn_grads or backbone_grads
             tower_grads = tower_grads or fpn_grads
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), fpn_grads=True) if fpn_grads else \
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), backbone_grads=True) if backbone_grads else \
+                self.get_loss_plan(*self.canvas_size(batched_inputs), fpn_grads=True) if fpn_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), tower_grads=True) if tower_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), pred_grads=True) if predictor_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), grads=True) if head_grads else \
@@ -341,6 +351,9 @@ class DD3D(nn.Module):
                 if fpn_grads:
                     bfeats, fparams = plan.fpn_grads()
                     towers, params = dict(towers, **bfeats), dict(params, **fparams)
+                if backbone_grads:
+                    l1, bparams = plan.backbone_grads()
+                    towers, params = dict(towers, **l1), dict(params, **bparams)
                 return losses, dict(plan.head_grads(), **towers), params
             return (losses, plan.head_grads()) if head_grads else losses
 

@@ -973,6 +973,114 @@ int dd3d_fpn_dgrad(const dd3d_fpn_grad_args* args, void* stream);
 int64_t dd3d_fpn_grad_slices(const dd3d_fpn_grad_args* args);
 int dd3d_fpn_grad_layout(int64_t* out, int32_t n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the DLA-34 backbone, level5 down to level2 (csrc/backbone_grads.hip): BasicBlock trees at most two deep without a
+ * residual root (dla.py:24-62, 206-247; BackboneLowering._tree).  n(.): the convolution's folded norm (layers.fold_norm, running
+ * statistics); every ReLU mask is [stored output > 0], from the tensor the forward left in the plan, in the storage it was left in.
+ * A depth-1 tree with input x and output `out`, G_t the gradient at a tensor t BEFORE t's own ReLU mask:
+ *   op            forward                                         backward
+ *   root          out = relu(n(root . [x2 | x1 | bottom | ...]))   dWr = wgrad([out > 0] G_out, cat), D_cat = dgrad([out > 0] G_out, Wr),
+ *                                                                  written once over the whole concat buffer and read by slices
+ *   tree2.conv2   x2 = relu(n(conv3x3(mid2)) + x1)                 g2 = [x2 > 0] D_cat[x2]: dW = wgrad(g2, mid2), G_mid2 = dgrad(g2, W)
+ *   tree2.conv1   mid2 = relu(n(conv3x3(x1)))                      dW = wgrad([mid2 > 0] G_mid2, x1),
+ *                                                                  G_x1 = (D_cat[x1] + [x2 > 0] D_cat[x2]) + dgrad([mid2 > 0] G_mid2, W)
+ *   tree1.conv2   x1 = relu(n(conv3x3(mid1)) + residual)           g1 = [x1 > 0] G_x1: dW = wgrad(g1, mid1), G_mid1 = dgrad(g1, W)
+ *   project       residual = n(project . bottom)    (no ReLU)      dWp = wgrad(g1, bottom), G_bottom = D_cat[bottom] + dgrad(g1, Wp)
+ *                 (the gradient at `residual` is g1: the call masks G_x1 by the stored x1; D_cat[bottom] only under level_root)
+ *   tree1.conv1   mid1 = relu(n(conv3x3_s(x)))                     dW = wgrad([mid1 > 0] G_mid1, x),
+ *                                                                  stride 2: C_x = F_x + dgrad_s2([mid1 > 0] G_mid1, W)
+ *                                                                  stride 1 (bottom = x): G_x = (A_x + g1) + dgrad([mid1 > 0] G_mid1, W)
+ *   max-pool      bottom = maxpool2x2(x)            (stride 2)     G_x = C_x + unpool(G_bottom): the window's arg-max receives it
+ * F_x: the FPN's gradient at x where x is a backbone output feature (backbone_level<n>), A_x: the root slice of x in an enclosing
+ * tree's concat gradient.  A depth-2 tree is [tree1 (depth 1, stride 2, writes t1 into the concat buffer of tree2) ; tree2 (depth 1,
+ * stride 1, input t1, root over [x2 | x1 | bottom | t1])]; under level_root the ONE pooled `bottom` is read by tree2's root and by
+ * tree1's project: G_bottom = D_cat2[bottom] + dgrad(g1, Wp) goes through the pool backward once.  The order of every sum is the order
+ * written here; none uses float atomics.
+ *
+ * dd3d_backbone_wgrad / dd3d_backbone_dgrad: ONE convolution per call, k x k (ksize 1 or 3), stride 1 or 2, padding (k - 1) / 2, output
+ * size ceil(H / stride); H, W are the INPUT's sizes.  With gm = g * [y > 0] (y NULL: gm = g):
+ *   dw_level[n][ky][kx][c] = sum_{b,oy,ox} gm[b,oy,ox,n] * x[b, oy s + ky - p, ox s + kx - p, c]     (zero padding; not scaled)
+ *   dw = scale[n] * dw_level        q[n] = sum gm        r[n] = sum_k dw_level[n][k] * w[n][k]
+ *   da[b,y,x,c] = (add[b,y,x,c] + res_g[b,y,x,c] * [res_y[b,y,x,c] > 0]) + sum_{n,ky,kx} scale[n] * gm[b,(y+p-ky)/s,(x+p-kx)/s,n] * w[n][ky][kx][c]
+ *     over the taps for which both divisions are exact; `add` and the res pair are optional (either alone is added to the sum as is).
+ * the same quantities as the towers' and the FPN's: the norm read-out is theirs (rstd * (r + (b_conv - mean) * q)).  Both are GEMMs on
+ * v_mfma_f32_32x32x2_f32 (exact f32 products, f32 accumulation): the weight gradient with per-slice partials summed in slice order; the
+ * input gradient with one fresh accumulator per 32-channel chunk of Cout (k k 32 terms in (tap, n) order), the chunks added in chunk
+ * order.  A zero or masked g enters the input gradient as an exact zero whatever scale holds.  One writer and a fixed order per sum: two
+ * runs agree bit for bit, whichever tile is picked.  Every word of dw_level, dw, q, r (wgrad) and of the Cin channels of da (dgrad) is
+ * written; nothing beyond them and the slab rows in use -- the other channels of a wider da buffer keep what they held.
+ *
+ * Every activation and gradient operand may be a channel slice of a wider buffer: f32 NHWC is a pointer at the slice's first channel
+ *   and the buffer's pitch; split planes are the pointer at the slice's first 32-channel chunk image (slices start on chunk boundaries).
+ *   x, y, res_y: DD3D_PG_ACT_* storages.  g, add, res_g, da: f32 NHWC with pitches g_pitch, add_pitch, res_pitch, da_pitch.
+ * part / qpart: dd3d_backbone_grad_slices(args) rows (host only; reads B, H, W, Cin, Cout, ksize, stride): units of 64 (stride 2: 32)
+ *   output pixels of a row, DD3D_BG_MIN_UNITS_PER_SLICE per slice at least, more once the slab would pass DD3D_TG_SLAB_BYTES.
+ * dgrad_rows / dgrad_group: rows (2, 4, 8) and input channels (128, 256) of the input gradient's block; 0 lets the call choose: the
+ *   largest of (8, 256), (4, 256), (2, 256) that gives DD3D_BG_MIN_TILES blocks, else (2, 128).  The result does not depend on them.
+ * dd3d_backbone_wgrad: three launches (reads x, y, g, w, scale).  dd3d_backbone_dgrad: one launch (reads y, g, w, scale, add, res_g,
+ *   res_y).  Safe under stream capture.
+ *
+ * dd3d_maxpool2x2_backward: da[b, 2y+i, 2x+j, c] = (add[...] or nothing) + (g'[b,y,x,c] if (i, j) is the window's arg-max else 0) with
+ *   g' = g, or g + res_g * [res_y > 0] (res_g alone when g is NULL): a strided tree without a project, whose pooled tensor is the block's
+ *   residual (max-pool row of the table: G_bottom = D_cat[bottom] + g1; it does not occur in DLA-34).  The arg-max is recomputed from the stored input x (H x W, both even, any DD3D_PG_ACT_* storage); among equal maxima the first in the
+ *   order (0,0), (0,1), (1,0), (1,1) wins (torch's max_pool2d backward on the CPU).  One launch.
+ * dd3d_backbone_grad_layout: sizeof and field offsets of both structs.
+ * Rejected (-1, dd3d_last_error starts with the entry point's name): Cin not a multiple of 32 or above DD3D_BG_MAX_CIN, Cout not a
+ *   multiple of 32 or above DD3D_BG_MAX_COUT, ksize outside {1, 3}, stride outside {1, 2}, pitches not a multiple of 4 or too small,
+ *   unknown storages, null pointers, res_g without res_y, too few slab rows, dgrad_rows outside {0, 2, 4, 8}, dgrad_group outside
+ *   {0, 128, 256}, more than DD3D_BG_MAX_PIXELS input pixels (B * H * W; the stride-2 level1 tensor of the 6 x 896 x 1600 nuScenes sample
+ *   has 2.15 million); the pool: odd sizes, C not a multiple of 32, the same pixel limit.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_BG_MAX_CIN 1280
+#define DD3D_BG_MAX_COUT 512
+#define DD3D_BG_UNIT 64
+#define DD3D_BG_MIN_UNITS_PER_SLICE 4
+#define DD3D_BG_MIN_TILES 512               /* two blocks per CU of 256; chosen like DD3D_FG_MIN_TILES, not measured */
+#define DD3D_BG_MAX_PIXELS (1l << 26)       /* B * H * W of a call's input: pixel, unit and block counts stay ints; words are longs */
+typedef struct dd3d_backbone_grad_args {    /* host memory; every pointer is device memory */
+  const void* x;                            /* convolution input [B][H][W], storage x_mode */
+  const void* y;                            /* stored output behind the ReLU [B][Ho][Wo], storage y_mode; NULL: no ReLU (project) */
+  const float* g;                           /* gradient at the output: [B][Ho][Wo][g_pitch] */
+  const float* w;                           /* [Cout][ksize][ksize][Cin] */
+  const float* scale;                       /* [Cout] */
+  const float* add;                         /* [B][H][W][add_pitch], or NULL */
+  const float* res_g;                       /* [B][H][W][res_pitch], or NULL: a gradient masked by res_y before it is added */
+  const void* res_y;                        /* stored tensor of the input's shape, storage res_y_mode (set with res_g) */
+  float* da;                                /* [B][H][W][da_pitch] */
+  float* part;                              /* scratch [n_slices][Cout][ksize * ksize * Cin] */
+  float* qpart;                             /* scratch [n_slices][Cout] */
+  float* dw_level;                          /* [Cout][ksize * ksize * Cin] */
+  float* dw;                                /* [Cout][ksize * ksize * Cin] */
+  float* q;                                 /* [Cout] */
+  float* r;                                 /* [Cout] */
+  int32_t B, H, W, Cin, Cout, ksize, stride;
+  int32_t g_pitch, add_pitch, res_pitch, da_pitch;
+  int32_t x_mode, x_pitch;                  /* DD3D_PG_ACT_*; floats per pixel (DD3D_PG_ACT_F32) */
+  int32_t y_mode, y_pitch;
+  int32_t res_y_mode, res_y_pitch;
+  int32_t n_slices;                         /* rows of part / qpart */
+  int32_t dgrad_rows, dgrad_group;
+  float x_plane_scale, y_plane_scale, res_y_plane_scale;  /* DD3D_PG_ACT_F16X2 */
+} dd3d_backbone_grad_args;
+typedef struct dd3d_pool_grad_args {        /* host memory; every pointer is device memory */
+  const void* x;                            /* the pool's stored input [B][H][W], storage x_mode */
+  const float* g;                           /* gradient at the pooled tensor: [B][H/2][W/2][g_pitch]; NULL with res_g alone */
+  const float* res_g;                       /* [B][H/2][W/2][res_pitch] or NULL: a second part, masked by res_y before it is added */
+  const void* res_y;                        /* stored tensor [B][H/2][W/2], storage res_y_mode (set with res_g) */
+  const float* add;                         /* [B][H][W][add_pitch], or NULL */
+  float* da;                                /* [B][H][W][da_pitch] */
+  int32_t B, H, W, C;
+  int32_t x_mode, x_pitch;
+  int32_t res_y_mode, res_y_pitch;
+  int32_t g_pitch, res_pitch, add_pitch, da_pitch;
+  float x_plane_scale, res_y_plane_scale;
+} dd3d_pool_grad_args;
+int dd3d_backbone_wgrad(const dd3d_backbone_grad_args* args, void* stream);
+int dd3d_backbone_dgrad(const dd3d_backbone_grad_args* args, void* stream);
+int64_t dd3d_backbone_grad_slices(const dd3d_backbone_grad_args* args);
+int dd3d_maxpool2x2_backward(const dd3d_pool_grad_args* args, void* stream);
+int dd3d_backbone_grad_layout(int64_t* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
