@@ -226,6 +226,13 @@ def nuscenes_sample_aggregate(instances, group_idxs, num_classes, poses, iou_thr
 
 
 # ----------------------------------------------------------------------------------------- NuscenesDD3D.forward
+def nuscenes_heads(sd, cls_tower_out):
+    """nuscenes_dd3d.py:371-374: the attribute logits and the rectified speed off the cls tower's output, per level."""
+    attr = [O.conv2d(sd, "attr_logits", t, padding=1) for t in cls_tower_out]
+    speed = [F.relu(O.conv2d(sd, "speed", t, padding=1)) for t in cls_tower_out]
+    return attr, speed
+
+
 def nuscenes_dd3d_forward(sd, cfg, batched_inputs):
     """nuscenes_dd3d.py:337-469, inference branch.  Inputs carry 'pose' = (quat wxyz, tvec) and 'sample_token'."""
     stages = {}
@@ -239,8 +246,7 @@ def nuscenes_dd3d_forward(sd, cfg, batched_inputs):
     logits, box2d_reg, centerness, cls_tower_out = O.fcos2d_head(sd, features, cfg["DD3D"]["FCOS2D"]["NUM_CLS_CONVS"],
                                                                      num_box_convs=cfg["DD3D"]["FCOS2D"]["NUM_BOX_CONVS"])
     quat, ctr, depth, size, conf = O.fcos3d_head(sd, features, cfg["DD3D"]["FCOS3D"]["NUM_CONVS"])
-    attr = [O.conv2d(sd, "attr_logits", t, padding=1) for t in cls_tower_out]  # nuscenes_dd3d.py:371-374
-    speed = [F.relu(O.conv2d(sd, "speed", t, padding=1)) for t in cls_tower_out]
+    attr, speed = nuscenes_heads(sd, cls_tower_out)
     heads = dict(logits=logits, box2d_reg=box2d_reg, centerness=centerness, quat=quat, ctr=ctr, depth=depth, size=size, conf=conf,
                  attr=attr, speed=speed, features=features)
     stages.update(heads)

@@ -28,13 +28,10 @@ def _cast(targets, dtype):
     return {k: (v.to(dtype) if k in FLOAT_TARGETS and torch.is_tensor(v) else v) for k, v in targets.items()}
 
 
-def head_grads(maps, targets, inv_K, p, upstream=None, dtype=torch.float64):
-    """d (sum_k upstream[k] * loss_k) / d maps by autograd through LO.losses in `dtype` (the conf target detached, as in the reference); `upstream`: 10 weights in the order of
-    OUT_INDEX (None: ones).  Returns {key<l>: NCHW gradient in `dtype`} for every head map of the case (zeros where the loss does not
-    reach a map)."""
-    fam = families(p)
-    L = p["num_levels"]
-    leaf = {f"{k}{l}": maps[f"{k}{l}"].detach().to(dtype).clone().requires_grad_(True) for k in fam for l in range(L)}
+def summed_loss(leaf, targets, inv_K, p, upstream=None, dtype=torch.float64):
+    """sum_k upstream[k] * loss_k of LO.losses on the maps `leaf` in `dtype` (`upstream`: 10 weights in the order of OUT_INDEX; None:
+    ones), the conf target detached as in the reference.  Returns (the sum, the loss dict).  The one statement of the scalar every
+    gradient oracle differentiates: head_grads with the head maps as leaves, whole_model_grad_oracle with the model's parameters."""
     out = LO.losses(leaf, _cast(targets, dtype), inv_K.to(dtype), p)
     if "loss_conf3d" in out and targets["pos_inds"].numel():
         # LO.losses leaves the entangled corner error attached to the graph; the reference detaches it before it becomes the conf
@@ -43,7 +40,17 @@ def head_grads(maps, targets, inv_K, p, upstream=None, dtype=torch.float64):
         cut = {k: (v.detach() if k[:-1] in ("quat", "ctr", "depth", "size") else v) for k, v in leaf.items()}
         out["loss_conf3d"] = LO.losses(cut, _cast(targets, dtype), inv_K.to(dtype), p)["loss_conf3d"]
     w = torch.ones(10, dtype=dtype) if upstream is None else torch.as_tensor(upstream).to(dtype)
-    total = sum(w[OUT_INDEX[k]] * v for k, v in out.items())
+    return sum(w[OUT_INDEX[k]] * v for k, v in out.items()), out
+
+
+def head_grads(maps, targets, inv_K, p, upstream=None, dtype=torch.float64):
+    """d (sum_k upstream[k] * loss_k) / d maps by autograd through LO.losses in `dtype` (the conf target detached, as in the reference); `upstream`: 10 weights in the order of
+    OUT_INDEX (None: ones).  Returns {key<l>: NCHW gradient in `dtype`} for every head map of the case (zeros where the loss does not
+    reach a map)."""
+    fam = families(p)
+    L = p["num_levels"]
+    leaf = {f"{k}{l}": maps[f"{k}{l}"].detach().to(dtype).clone().requires_grad_(True) for k in fam for l in range(L)}
+    total, _ = summed_loss(leaf, targets, inv_K, p, upstream, dtype)
     g = torch.autograd.grad(total, list(leaf.values()), allow_unused=True)
     return {k: (torch.zeros_like(v) if gi is None else gi) for (k, v), gi in zip(leaf.items(), g)}
 

@@ -17,6 +17,7 @@ import torch
 from tests import backbone_grad_cases as BC
 from tests import backbone_grad_oracle as BO
 from tests import loss_grad_cases as GC
+from tests.util import decode
 
 pytestmark = pytest.mark.gpu
 
@@ -390,22 +391,6 @@ def test_slice_count_is_a_pure_shape_query(hiplib):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- end to end
-def decode(buf, c0=0, n=None):
-    """NCHW float32 values of channels c0 .. c0 + n of a plan buffer IN THE STORAGE act_binding picks: its split planes where it has them."""
-    n = buf.pitch - c0 if n is None else n
-    if buf.p is None:
-        return buf.t[..., c0:c0 + n].permute(0, 3, 1, 2).float().cpu().contiguous()
-    k0, k1 = c0 // 32, (c0 + n + 31) // 32
-    if buf.f16:
-        terms = buf.p[k0:k1].view(torch.float16).float()
-        x = (terms[:, :, 0] + terms[:, :, 1]) * (1.0 / buf.plane_scale)
-    else:
-        terms = (buf.p[k0:k1].to(torch.int32) << 16).view(torch.float32)
-        x = (terms[:, :, 0] + terms[:, :, 1]) + terms[:, :, 2]
-    x = x.permute(1, 0, 2).reshape(buf.B, buf.H, buf.W, (k1 - k0) * 32)
-    return x[..., c0 - 32 * k0:c0 - 32 * k0 + n].permute(0, 3, 1, 2).cpu().contiguous()
-
-
 def _end_to_end(exp, weights, B, H, W, ds, math=None, act_scale=None, empty=(1, )):
     from dd3d_amd.synthetic import make_gt_instances, make_inputs
     from tests.test_loss_grads_gpu import _model

@@ -115,3 +115,19 @@ def candidate_margins(plan, st, cfg, b=0, ref_b=None):
             d = min(d, abs(float(rank[flat]) - kth))
         margins.append(d)
     return len(hip_keys), len(ref_keys), margins
+
+
+def decode(buf, c0=0, n=None):
+    """NCHW float32 values of channels c0 .. c0 + n of a plan buffer IN THE STORAGE act_binding picks: its split planes where it has them."""
+    n = buf.pitch - c0 if n is None else n
+    if buf.p is None:
+        return buf.t[..., c0:c0 + n].permute(0, 3, 1, 2).float().cpu().contiguous()
+    k0, k1 = c0 // 32, (c0 + n + 31) // 32
+    if buf.f16:
+        terms = buf.p[k0:k1].view(torch.float16).float()
+        x = (terms[:, :, 0] + terms[:, :, 1]) * (1.0 / buf.plane_scale)
+    else:
+        terms = (buf.p[k0:k1].to(torch.int32) << 16).view(torch.float32)
+        x = (terms[:, :, 0] + terms[:, :, 1]) + terms[:, :, 2]
+    x = x.permute(1, 0, 2).reshape(buf.B, buf.H, buf.W, (k1 - k0) * 32)
+    return x[..., c0 - 32 * k0:c0 - 32 * k0 + n].permute(0, 3, 1, 2).cpu().contiguous()
