@@ -35,6 +35,9 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct StemFusedK {
   dd3d_stem_args a;
+  float* keep_base;     // the KEEP instantiation only (dd3d_stem_fused_keep_f16x2): [B][Hp][Wp][pitch] f32
+  float* keep_level0;
+  int32_t keep_base_pitch, keep_level0_pitch;
 };
 
 // (Measured, profiles/r04w_stem_tile_variants.txt: an 8 x 16 tile on 4-wave blocks -- 78 KiB of LDS, two blocks per CU at different phases -- 164 us
@@ -99,6 +102,26 @@ __device__ __forceinline__ int sf_store_tile(unsigned char* plane_hi, int plane_
   return ovf;
 }
 
+// KEEP: the canvas pixels [2 oh0, 2 oh0 + 2 SF_TH) x [2 ow0, 2 ow0 + 2 SF_TW) of a finished 16-channel tile (two planes of halves in LDS,
+// `cols` pixels a row, the block's first owned pixel at tile position (off, off)) -> f32 NHWC in HBM: the decoded value (hi + lo) /
+// plane scale, what the next layer consumed.  A halo pixel is not stored: the block that owns it writes the same bits.
+__device__ __forceinline__ void sf_keep_tile(const unsigned char* plane_hi, int plane_bytes, int cols, int off, float* dst, int pitch, int b, int oh0, int ow0,
+                                             int Hp, int Wp, float pscale, int tid) {
+  for (int i = tid; i < 2 * SF_TH * 2 * SF_TW * 4; i += 64 * SF_WAVES) {
+    const int p = i >> 2, c4 = (i & 3) * 4;
+    const int dr = p / (2 * SF_TW), dc = p - dr * (2 * SF_TW);
+    const int r = 2 * oh0 + dr, c = 2 * ow0 + dc;
+    if (r >= Hp || c >= Wp) continue;
+    const unsigned char* src = plane_hi + ((dr + off) * cols + dc + off) * 32 + c4 * 2;
+    const f16x4 hi = *reinterpret_cast<const f16x4*>(src), lo = *reinterpret_cast<const f16x4*>(src + plane_bytes);
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = ((float)hi[e] + (float)lo[e]) / pscale;
+    *reinterpret_cast<f32x4*>(dst + (((long)b * Hp + r) * Wp + c) * pitch + c4) = v;
+  }
+}
+
+template <bool KEEP>
 __global__ __launch_bounds__(64 * SF_WAVES) void stem_fused_f16x2_kernel(const StemFusedK P) {
   const dd3d_stem_args& a = P.a;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -234,6 +257,7 @@ __global__ __launch_bounds__(64 * SF_WAVES) void stem_fused_f16x2_kernel(const S
       aoff[ch] = ((t / 3) * SF_CB + (t % 3)) * 32 + (q4 & 1) * 16;
     }
     __syncthreads();  // base tile complete; the image patch is dead
+    if constexpr (KEEP) sf_keep_tile(regB, SF_B_PLANE, SF_CB, 2, P.keep_base, P.keep_base_pitch, b, oh0, ow0, a.Hp, a.Wp, pscale, tid);
     const int r00 = 2 * oh0 - 1, c00 = 2 * ow0 - 1;
     const auto outside = [&](int po) {
       const int pr = po / SF_C0, pc = po - pr * SF_C0;
@@ -294,6 +318,7 @@ __global__ __launch_bounds__(64 * SF_WAVES) void stem_fused_f16x2_kernel(const S
       aoff[ch] = ((t / 3) * SF_C0 + (t % 3)) * 32 + (q4 & 1) * 16;
     }
     __syncthreads();  // level0 tile complete; the base tile is dead
+    if constexpr (KEEP) sf_keep_tile(regA, SF_0_PLANE, SF_C0, 1, P.keep_level0, P.keep_level0_pitch, b, oh0, ow0, a.Hp, a.Wp, pscale, tid);
     float* stage = reinterpret_cast<float*>(regB);  // [256 pixels][32 channels] f32
     constexpr int U3 = SF_U >= 4 ? 2 : 1;  // groups per iteration (each has two output-channel halves = two chains)
     for (int g0 = wave; g0 < SF_G1; g0 += U3 * SF_WAVES) {
@@ -369,25 +394,44 @@ __global__ __launch_bounds__(64 * SF_WAVES) void stem_fused_f16x2_kernel(const S
 
 }  // namespace dd3d
 
-extern "C" int dd3d_stem_fused_f16x2(const dd3d_stem_args* a, void* stream) {
+// the checks and the launch of both entry points; `keep`: NULL for dd3d_stem_fused_f16x2
+static int stem_fused_launch(const dd3d_stem_args* a, const dd3d_stem_keep_args* keep, const char* who, void* stream) {
   using namespace dd3d;
   DD3D_REQUIRE(a && a->src && a->sizes && a->w1 && a->w2 && a->w3 && a->scale1 && a->bias1 && a->scale2 && a->bias2 && a->scale3 && a->bias3,
-               "dd3d_stem_fused_f16x2: null pointer");
-  DD3D_REQUIRE(a->out || a->out_planes, "dd3d_stem_fused_f16x2: no output");
-  DD3D_REQUIRE(a->B > 0 && a->Hp > 0 && a->Wp > 0 && (a->Hp % 2) == 0 && (a->Wp % 2) == 0, "dd3d_stem_fused_f16x2: canvas %dx%d (x%d) must be even", a->Hp,
-               a->Wp, a->B);
-  DD3D_REQUIRE(!a->out || (a->out_pitch >= 32 && a->out_pitch % 4 == 0), "dd3d_stem_fused_f16x2: out_pitch=%d", a->out_pitch);
-  DD3D_REQUIRE(a->plane_scale > 0.f, "dd3d_stem_fused_f16x2: plane_scale=%g", (double)a->plane_scale);
+               "%s: null pointer", who);
+  DD3D_REQUIRE(a->out || a->out_planes, "%s: no output", who);
+  DD3D_REQUIRE(a->B > 0 && a->Hp > 0 && a->Wp > 0 && (a->Hp % 2) == 0 && (a->Wp % 2) == 0, "%s: canvas %dx%d (x%d) must be even", who, a->Hp, a->Wp, a->B);
+  DD3D_REQUIRE(!a->out || (a->out_pitch >= 32 && a->out_pitch % 4 == 0), "%s: out_pitch=%d", who, a->out_pitch);
+  DD3D_REQUIRE(a->plane_scale > 0.f, "%s: plane_scale=%g", who, (double)a->plane_scale);
   DD3D_REQUIRE((a->K == nullptr) == (a->inv_K == nullptr) && a->zero_count >= 0 && (a->zero_count == 0 || a->zero_f32),
-               "dd3d_stem_fused_f16x2: K and inv_K come together; zero_count=%d needs zero_f32", a->zero_count);
-  static unsigned long long attr_done[4];
-  if (lds_opt_in_needed(attr_done)) {
-    if (lds_opt_in(reinterpret_cast<const void*>(stem_fused_f16x2_kernel), (size_t)SF_LDS, "stem_fused_f16x2_kernel") != DD3D_OK) return DD3D_E_LAUNCH;
-    lds_opt_in_done(attr_done);  // (every opt-in of this call site succeeded on this device)
+               "%s: K and inv_K come together; zero_count=%d needs zero_f32", who, a->zero_count);
+  if (keep) {
+    DD3D_REQUIRE(keep->keep_base && keep->keep_level0, "%s: no keep_base / keep_level0", who);
+    DD3D_REQUIRE(keep->keep_base_pitch >= 16 && keep->keep_base_pitch % 4 == 0 && keep->keep_level0_pitch >= 16 && keep->keep_level0_pitch % 4 == 0,
+                 "%s: keep pitches %d, %d must be multiples of 4 and hold 16 channels", who, keep->keep_base_pitch, keep->keep_level0_pitch);
+    DD3D_REQUIRE(reinterpret_cast<uintptr_t>(keep->keep_base) % 16 == 0 && reinterpret_cast<uintptr_t>(keep->keep_level0) % 16 == 0,
+                 "%s: keep_base / keep_level0 are not 16-byte aligned", who);
+  }
+  const void* kernel = keep ? reinterpret_cast<const void*>(stem_fused_f16x2_kernel<true>) : reinterpret_cast<const void*>(stem_fused_f16x2_kernel<false>);
+  static unsigned long long attr_done[2][4];
+  if (lds_opt_in_needed(attr_done[keep ? 1 : 0])) {
+    if (lds_opt_in(kernel, (size_t)SF_LDS, "stem_fused_f16x2_kernel") != DD3D_OK) return DD3D_E_LAUNCH;
+    lds_opt_in_done(attr_done[keep ? 1 : 0]);  // (every opt-in of this call site succeeded on this device)
   }
   StemFusedK P;
   P.a = *a;
+  P.keep_base = keep ? keep->keep_base : nullptr, P.keep_level0 = keep ? keep->keep_level0 : nullptr;
+  P.keep_base_pitch = keep ? keep->keep_base_pitch : 0, P.keep_level0_pitch = keep ? keep->keep_level0_pitch : 0;
   const int Ho = a->Hp / 2, Wo = a->Wp / 2;
-  hipLaunchKernelGGL(stem_fused_f16x2_kernel, dim3(ceil_div(Wo, SF_TW), ceil_div(Ho, SF_TH), a->B), dim3(64 * SF_WAVES), SF_LDS, reinterpret_cast<hipStream_t>(stream), P);
+  const dim3 grid(ceil_div(Wo, SF_TW), ceil_div(Ho, SF_TH), a->B);
+  if (keep) hipLaunchKernelGGL(stem_fused_f16x2_kernel<true>, grid, dim3(64 * SF_WAVES), SF_LDS, reinterpret_cast<hipStream_t>(stream), P);
+  else hipLaunchKernelGGL(stem_fused_f16x2_kernel<false>, grid, dim3(64 * SF_WAVES), SF_LDS, reinterpret_cast<hipStream_t>(stream), P);
   return check_launch("stem_fused_f16x2_kernel");
+}
+
+extern "C" int dd3d_stem_fused_f16x2(const dd3d_stem_args* a, void* stream) { return stem_fused_launch(a, nullptr, "dd3d_stem_fused_f16x2", stream); }
+
+extern "C" int dd3d_stem_fused_keep_f16x2(const dd3d_stem_keep_args* k, void* stream) {
+  DD3D_REQUIRE(k != nullptr, "dd3d_stem_fused_keep_f16x2: null args");
+  return stem_fused_launch(&k->stem, k, "dd3d_stem_fused_keep_f16x2", stream);
 }

@@ -81,7 +81,8 @@ class ForwardPlan(PlanBase, BackboneLowering):
         self.fused_stem = self._can_fuse_stem(bb.bottom_up) if isinstance(bb.bottom_up, DLA) else False
         self._norm = ((C.c_float * 3)(*[float(v) for v in model.pixel_mean.flatten().tolist()]),
                       (C.c_float * 3)(*[float(v) for v in model.pixel_std.flatten().tolist()]))
-        img = self.buf("img4", B, Hp, Wp, 4) if (not self.fused_stem or self.dry_run) else None
+        stem_grads = bool(getattr(self, "with_stem_grads", False))  # (LossPlan(stem_grads=True): base_layer's weight gradient reads the image)
+        img = self.buf("img4", B, Hp, Wp, 4) if (not self.fused_stem or self.dry_run or stem_grads) else None
 
         def _pre(lib, st, img=img):
             self.amax[:max(1, len(self.amax_names))].zero_()  # (captured with the rest of the forward: the maxima are per forward)
@@ -98,6 +99,13 @@ class ForwardPlan(PlanBase, BackboneLowering):
         self.stem_begins_forward = bool(self.fused_stem and not self.dry_run and os.environ.get("DD3D_STEM_BEGIN", "1") != "0")
         if not self.stem_begins_forward:
             self.ops.append(CallOp(_pre, "preprocess", dict(kind="preprocess", img=img, mean=list(self._norm[0]), std=list(self._norm[1]))))
+        elif stem_grads:  # the fused stem still reads the uint8 input itself; the normalised canvas is written for the backward alone
+
+            def _img(lib, st, img=img):
+                hip.check(lib.dd3d_preprocess_u8_nhwc4(self.in_u8.data_ptr(), self.in_sizes.data_ptr(), img.t.data_ptr(), B, Hp, Wp, self._norm[0],
+                                                       self._norm[1], st), "preprocess")
+
+            self.ops.append(CallOp(_img, "preprocess", dict(kind="preprocess", img=img, mean=list(self._norm[0]), std=list(self._norm[1]))))
 
         # ---- backbone + FPN
         img_view = img.view() if img is not None else None  # (None: the fused stem reads the uint8 input itself)

@@ -3,8 +3,8 @@ the dict's weighted sum with respect to the head maps (csrc/loss_grads.hip) and,
 layer's parameters and the tower outputs it reads (csrc/predictor_grads.hip), and one layer further again through the head towers to
 their parameters and the FPN outputs (csrc/tower_grads.hip), and one stage further through the FPN to its parameters and the backbone's
 output features (csrc/fpn_grads.hip), and one stage further again through the DLA-34 backbone's level5 .. level2 to their parameters
-and the stem's output (csrc/backbone_grads.hip).  The backward stops there: the stem (base_layer, level0, level1) has none, and there
-is no optimiser, batch-statistics norm or model.train().
+and the stem's output (csrc/backbone_grads.hip), and last through the stem -- base_layer, level0, level1 -- to its parameters
+(csrc/stem_grads.hip).  There is no optimiser, batch-statistics norm or model.train().
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -568,6 +568,67 @@ class PoolGrads:
         return all(bool((t[n:] == fill).all()) for t, n in self._raw)
 
 
+class StemConvGrads:
+    """Buffers and dd3d_stem_grad_args of ONE stem convolution (csrc/stem_grads.hip): (ksize, stride, Cin, Cout) one of
+    hip.STEM_GRAD_SHAPES.
+
+    `H`, `W`: the INPUT's sizes; `x`: [B, H, W, Cin] f32, possibly a channel slice of a wider tensor (None for a call that only runs the
+    input gradient); `y`: (mode, device address, pitch, plane scale) of the stored output whose ReLU the gradient crosses; `g`:
+    [B, Ho, Wo, Cout] f32 gradient at the output (a slice may be given); `w`: [Cout, k, k, Cin]; `scale`: [Cout]; `da`: a [B, H, W, Cin]
+    slice of a wider gradient buffer to write into, or None to allocate it; `slab`: (part, qpart) shared with other calls that run in
+    stream order, or None to allocate them; `wgrad_blocks`: blocks of the weight gradient's main launch (0: one per slice).  Outputs are
+    allocated here, filled with `fill` and followed by `guard` words of it."""
+    def __init__(self, device, B, H, W, Cin, Cout, ksize, stride, x, y, g, w, scale, da=None, slab=None, fill=0.0, guard=0, wgrad_blocks=0,
+                 wgrad=True, dgrad=True):
+        self.B, self.H, self.W, self.Cin, self.Cout, self.ksize, self.stride = B, int(H), int(W), Cin, Cout, ksize, stride
+        self.Ho, self.Wo = (self.H + stride - 1) // stride, (self.W + stride - 1) // stride
+        self.keep = (x, g, w, scale, slab)
+        self.scale = scale
+        self.with_wgrad, self.with_dgrad = bool(wgrad), bool(dgrad)
+        a = hip.StemGradArgs()
+        self._raw = []
+
+        def out(*shape):
+            numel = int(np.prod(shape))
+            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
+            self._raw.append((t, numel))
+            return t[:numel].view(*shape)
+
+        pitch = lambda t: int(t.stride(-2)) if t.shape[-2] > 1 or t.stride(-2) >= t.shape[-1] else int(t.shape[-1])
+        KK = ksize * ksize * Cin
+        assert tuple(g.shape) == (B, self.Ho, self.Wo, Cout) and g.stride(-1) == 1, (tuple(g.shape), (B, self.Ho, self.Wo, Cout))
+        self.n_slices = hip.stem_grad_slices(B, self.H, self.W, Cin, Cout, ksize, stride)
+        self.part = self.qpart = self.dw_level = self.dw = self.q = self.r = self.da = None
+        if wgrad:
+            assert tuple(x.shape) == (B, self.H, self.W, Cin) and x.stride(-1) == 1, (tuple(x.shape), (B, self.H, self.W, Cin))
+            if slab is None:
+                slab = (out(self.n_slices, Cout, KK), out(self.n_slices, Cout))
+            self.part, self.qpart = slab
+            assert self.part.numel() >= self.n_slices * Cout * KK and self.qpart.numel() >= self.n_slices * Cout
+            self.dw_level, self.dw, self.q, self.r = out(Cout, KK), out(Cout, KK), out(Cout), out(Cout)
+            a.part, a.qpart, a.dw_level, a.dw = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw))
+            a.q, a.r = self.q.data_ptr(), self.r.data_ptr()
+            a.x, a.x_pitch = x.data_ptr(), pitch(x)
+        if dgrad:
+            self.da = out(B, self.H, self.W, Cin) if da is None else da
+            assert tuple(self.da.shape) == (B, self.H, self.W, Cin) and self.da.stride(-1) == 1
+            a.da, a.da_pitch = self.da.data_ptr(), pitch(self.da)
+        a.y, a.y_mode, a.y_pitch, a.y_plane_scale = y[1] or None, int(y[0]), int(y[2]), float(y[3])
+        a.g, a.w, a.scale, a.g_pitch = g.data_ptr(), w.data_ptr(), scale.data_ptr(), pitch(g)
+        a.B, a.H, a.W, a.Cin, a.Cout, a.ksize, a.stride = int(B), self.H, self.W, int(Cin), int(Cout), int(ksize), int(stride)
+        a.n_slices, a.wgrad_blocks = self.n_slices, int(wgrad_blocks)
+        self.args = a
+
+    def launch(self, lib, st):
+        if self.with_wgrad:
+            hip.check(lib.dd3d_stem_wgrad(C.byref(self.args), st), "stem_wgrad")
+        if self.with_dgrad:
+            hip.check(lib.dd3d_stem_dgrad(C.byref(self.args), st), "stem_dgrad")
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
 def slice_binding(bind, c0, npix):
     """The binding (mode, address, pitch, plane scale) of the channel slice that starts at channel `c0` of a stored buffer with `npix`
     pixels: f32 moves the pointer by channels, split planes by whole 32-channel chunk images (f16x2: 128, bf16x3: 192 bytes a pixel)."""
@@ -862,10 +923,15 @@ class LossPlan(ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
     def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
-                 fpn_grads=False, backbone_grads=False):
-        self.with_backbone_grads = bool(backbone_grads)  # (`backbone_grads`, `fpn_grads` and `tower_grads` themselves are the read-out methods)
+                 fpn_grads=False, backbone_grads=False, stem_grads=False):
+        self.with_stem_grads = bool(stem_grads)  # (read by the trunk: the stem keeps its intermediates and the normalised image)
+        # (`backbone_grads`, `fpn_grads` and `tower_grads` themselves are the read-out methods)
+        self.with_backbone_grads = bool(backbone_grads) or self.with_stem_grads
         if self.with_backbone_grads:  # before anything is built or launched
             check_dla_backward(model.backbone.bottom_up, model)
+        if self.with_stem_grads and (int(Hp) % 2 or int(Wp) % 2):
+            raise NotImplementedError(f"stem gradients need an even canvas ({Hp} x {Wp}): the stem's lowering sizes level1 as floor(H / 2), the stride-2 "
+                                      "backward as ceil(H / 2); canvases padded to the FPN's size divisibility are always even")
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
         self.with_fpn_grads = bool(fpn_grads) or self.with_backbone_grads
         self.keep_tower_outputs = bool(tower_grads) or self.with_fpn_grads
@@ -935,6 +1001,8 @@ class LossPlan(ForwardPlan):
             self._fpn_grads(model)
         if self.with_backbone_grads:
             self._backbone_grads(model)
+        if self.with_stem_grads:
+            self._stem_grads(model)
 
     def _loss_grads(self, a):
         """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
@@ -1114,8 +1182,8 @@ class LossPlan(ForwardPlan):
     def _backbone_grads(self, model):
         """The DLA-34 backbone's backward behind the FPN's (include/dd3d_hip.h states it; `dla_backward` lays out the calls): level5 down
         to level2, one weight-gradient and one input-gradient call per convolution and one launch per 2x2 max-pool, on the main stream --
-        still one hipGraph.  The stem (base_layer, level0, level1) stays frozen: the chain ends at the gradient of the tensor level2
-        reads.  Every call shares the one slab of weight-gradient partials, sized for its largest user."""
+        still one hipGraph.  The chain ends at the gradient of the tensor level2 reads; LossPlan(stem_grads=True) goes on from
+        there (_stem_grads).  Every call shares the one slab of weight-gradient partials, sized for its largest user."""
         dev, B = self.device, self.B
         dla = model.backbone.bottom_up
         l1 = self.bufs[f"level1.{len(dla.level1) - 1}"].view()  # the stem's output, fused or launch by launch
@@ -1167,6 +1235,54 @@ class LossPlan(ForwardPlan):
             raise RuntimeError("this LossPlan was built without backbone_grads=True")
         named = {id(p): k for k, p in self.model.named_parameters()}
         return {"backbone_level1": self.level1_grad.permute(0, 3, 1, 2).clone()}, dla_param_grads(named, self.backbone_layers)
+
+    def _stem_grads(self, model):
+        """The stem's backward behind the backbone's (csrc/stem_grads.hip; include/dd3d_hip.h states it): level1.0 and level0.0 (weight
+        and input gradient), then base_layer (weight gradient; the image has none), on the main stream -- still one hipGraph.  The calls
+        read the f32 tensors `img4`, `base` and `level0.0` -- the launch-by-launch stem's own buffers, or what the fused stem's KEEP launch
+        and the preprocess launch store for them -- and take the three ReLU masks from `base`, `level0.0` and the stored `level1.0`.  The
+        calls share the plan's slab of weight-gradient partials; it never grows for them (a stem slice is at most 32 x 196 words)."""
+        from dd3d_amd.layers import fold_norm
+        dev, B = self.device, self.B
+        dla = model.backbone.bottom_up
+        convs = [("base_layer", dla.base_layer, "img4", "base"), ("level0.0", dla.level0[0], "base", "level0.0"), ("level1.0", dla.level1[0], "level0.0", "level1.0")]
+        assert len(dla.level0) == 1 and len(dla.level1) == 1, "the stem's backward covers one level0 and one level1 convolution (every DLA)"
+        part, qpart = self.tower_slab
+        self.stem_layers = OrderedDict()
+        g = self.level1_grad
+        for key, conv, xname, yname in reversed(convs):
+            xb, yv = self.bufs[xname], self.bufs[yname].view()
+            cout, cin, k = int(conv.weight.shape[0]), int(xb.pitch), int(conv.weight.shape[-1])
+            assert (k, int(conv.stride), cin, cout) in hip.STEM_GRAD_SHAPES and xb.has_f32 and xb.t is not None, (key, k, conv.stride, cin, cout)
+            w = torch.zeros((cout, k, k, cin), dtype=torch.float32)
+            w[..., :conv.weight.shape[1]] = conv.weight.detach().float().permute(0, 2, 3, 1)  # (the image's fourth channel: a zero filter)
+            n = hip.stem_grad_slices(B, xb.H, xb.W, cin, cout, k, int(conv.stride))
+            assert n * cout * k * k * cin <= part.numel() and n * cout <= qpart.numel(), \
+                f"stem_grads.{key}: {n} slices of {cout} x {k * k * cin} words do not fit the plan's slab of {part.numel()} words"
+            lay = StemConvGrads(dev, B, xb.H, xb.W, cin, cout, k, int(conv.stride), xb.t, act_binding(self, yv), g, w.to(dev), self._vec(fold_norm(conv, None)[0]),
+                                slab=self.tower_slab, dgrad=key != "base_layer")
+            lay.conv, lay.src = conv, dict(x=(xname, 0, cin), y=(yname, 0, cout))
+            self.stem_layers[key] = lay
+            self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), "stem_grads." + key, dict(kind="stem_grads", layer=key)))
+            g = lay.da
+        # as for the backbone: every stored tensor read above must still hold the forward's values when the backward runs
+        self.stem_reads = ["img4", "base", "level0.0", "level1.0"]
+        for name in self.stem_reads:
+            assert name in self.bufs, f"the buffer {name!r} the stem backward reads does not exist"
+        if not self.dry_run:
+            addrs = [(v.pptr or v.ptr) for v in (self.bufs[n].view() for n in self.stem_reads)]
+            assert len(set(addrs)) == len(addrs) and all(addrs), "two tensors the stem backward reads share storage"
+
+    def stem_grads(self):
+        """(the gradients at level0's and base_layer's outputs, the stem's parameter gradients) of the last run, copies:
+        {backbone_level0, backbone_base_layer: (B, 16, Hp, Wp)} -- neither masked by its tensor's own ReLU yet -- and {name in
+        model.named_parameters(): tensor of the parameter's shape} for backbone.bottom_up.base_layer / level0.0 / level1.0, float32."""
+        if not self.with_stem_grads:
+            raise RuntimeError("this LossPlan was built without stem_grads=True")
+        named = {id(p): k for k, p in self.model.named_parameters()}
+        tens = {"backbone_level0": self.stem_layers["level1.0"].da.permute(0, 3, 1, 2).clone(),
+                "backbone_base_layer": self.stem_layers["level0.0"].da.permute(0, 3, 1, 2).clone()}
+        return tens, dla_param_grads(named, self.stem_layers)
 
     def tower_grads(self):
         """(FPN-output gradients, tower parameter gradients) of the last run, copies: {feature<l>: (B, C, h_l, w_l)} and {name in

@@ -17,14 +17,22 @@ from dd3d_amd.engine.tiling import MATH_TILES, PLANE_TILES, ROW_ONLY_TILES, choo
 
 class FusedStemOp:
     """One dd3d_stem_fused_f16x2 launch: uint8 image -> normalise -> base_layer -> level0 -> level1 (DLA, dla.py:271-280,327-344), the
-    intermediate maps kept in LDS.  Replaces preprocess + three convolutions + the plane split of level1's output."""
-    def __init__(self, plan, model, convs, vout, name="stem"):
+    intermediate maps kept in LDS.  Replaces preprocess + three convolutions + the plane split of level1's output.  `keep`: (base, level0)
+    f32 views the launch also stores its base_layer and level0 outputs into (dd3d_stem_fused_keep_f16x2: a plan that runs the stem's
+    backward); out / out_planes hold the same bits either way."""
+    def __init__(self, plan, model, convs, vout, name="stem", keep=None):
         from dd3d_amd.layers import fold_norm
         assert plan.math == hip.MATH_F16X2
         self.name, self.macs = name, 0
         B, Hp, Wp = plan.B, plan.Hp, plan.Wp
-        a = hip.StemArgs()
+        self.keep_args = hip.StemKeepArgs() if keep is not None else None
+        a = self.keep_args.stem if keep is not None else hip.StemArgs()
         self.keep = []
+        if keep is not None:
+            kb, k0 = keep
+            assert kb.has_f32 and k0.has_f32 and (kb.C, k0.C) == (16, 16) and (kb.H, kb.W, k0.H, k0.W) == (Hp, Wp, Hp, Wp)
+            k = self.keep_args
+            k.keep_base, k.keep_level0, k.keep_base_pitch, k.keep_level0_pitch = kb.ptr or None, k0.ptr or None, kb.pitch, k0.pitch
         descs = []
         for i, (conv, cin_p) in enumerate(zip(convs, (4, 16, 16)), 1):
             planes, row_scale = pack_smallc_f16x2(conv.weight, cin_p)
@@ -54,7 +62,7 @@ class FusedStemOp:
         self.plan, self.begin_forward = plan, False
         self.a = a
         self.desc = dict(kind="fused_stem", convs=descs, vout=vout, mean=[float(v) for v in model.pixel_mean.flatten()],
-                         std=[float(v) for v in model.pixel_std.flatten()], planes=bool(vout.np))
+                         std=[float(v) for v in model.pixel_std.flatten()], planes=bool(vout.np), keep=keep)
         self.info = dict(name=name, M=B * (Hp // 2) * (Wp // 2), N=32, K=0, tile="fused", splitk=1, math=hip.MATH_F16X2, blocks=0, nsegs=1)
 
     def __call__(self, lib, stream):
@@ -63,7 +71,10 @@ class FusedStemOp:
             a.K, a.inv_K = p.in_K.data_ptr(), p.inv_K.data_ptr()
             n = max(1, len(p.amax_names))
             a.zero_f32, a.zero_count = p.amax.data_ptr(), n * p.amax.shape[1] * p.amax.shape[2]
-        hip.check(lib.dd3d_stem_fused_f16x2(C.byref(self.a), stream), "fused stem " + self.name)
+        if self.keep_args is not None:
+            hip.check(lib.dd3d_stem_fused_keep_f16x2(C.byref(self.keep_args), stream), "fused stem (keep) " + self.name)
+        else:
+            hip.check(lib.dd3d_stem_fused_f16x2(C.byref(self.a), stream), "fused stem " + self.name)
 
 
 class SmallcConvOp:

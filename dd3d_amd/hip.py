@@ -76,6 +76,11 @@ class StemArgs(C.Structure):
     ]
 
 
+class StemKeepArgs(C.Structure):
+    """`dd3d_stem_keep_args`."""
+    _fields_ = [("stem", StemArgs), ("keep_base", C.c_void_p), ("keep_level0", C.c_void_p), ("keep_base_pitch", C.c_int32), ("keep_level0_pitch", C.c_int32)]
+
+
 class ResizeArgs(C.Structure):
     """`dd3d_resize_args`."""
     _fields_ = [
@@ -334,18 +339,47 @@ def backbone_grad_slices(B, H, W, Cin, Cout, ksize, stride):
     return (units + ups - 1) // ups
 
 
+SG_UNIT, SG_TARGET_SLICES, SG_MIN_UNITS_PER_SLICE, SG_MAX_UNITS_PER_SLICE = 64, 512, 8, 64
+STEM_GRAD_SHAPES = ((7, 1, 4, 16), (3, 1, 16, 16), (3, 2, 16, 32))  # (ksize, stride, Cin, Cout) of base_layer, level0.0, level1.0
+
+
+class StemGradArgs(C.Structure):
+    """`dd3d_stem_grad_args`."""
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("g", C.c_void_p), ("w", C.c_void_p), ("scale", C.c_void_p), ("da", C.c_void_p),
+        ("part", C.c_void_p), ("qpart", C.c_void_p), ("dw_level", C.c_void_p), ("dw", C.c_void_p), ("q", C.c_void_p), ("r", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("ksize", C.c_int32),
+        ("stride", C.c_int32), ("x_pitch", C.c_int32), ("g_pitch", C.c_int32), ("da_pitch", C.c_int32), ("y_mode", C.c_int32),
+        ("y_pitch", C.c_int32), ("n_slices", C.c_int32), ("wgrad_blocks", C.c_int32), ("y_plane_scale", C.c_float)
+    ]
+
+
+def stem_grad_slices(B, H, W, Cin, Cout, ksize, stride):
+    """Rows of `part` / `qpart` one dd3d_stem_wgrad call needs (the rule of dd3d_stem_grad_slices, for plans built without a device).
+    H, W: the INPUT's sizes; a unit is up to 64 output pixels of a row; about SG_TARGET_SLICES slices of 8 to 64 units, more units once the
+    slab would pass TG_SLAB_BYTES."""
+    ho, wo = (H + stride - 1) // stride, (W + stride - 1) // stride
+    units = B * ho * ((wo + SG_UNIT - 1) // SG_UNIT)
+    ups = min(max((units + SG_TARGET_SLICES - 1) // SG_TARGET_SLICES, SG_MIN_UNITS_PER_SLICE), SG_MAX_UNITS_PER_SLICE)
+    max_slices = TG_SLAB_BYTES // (Cout * ksize * ksize * Cin * 4)
+    if ups * max_slices < units:
+        ups = (units + max_slices - 1) // max_slices
+    return (units + ups - 1) // ups
+
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
     "dd3d_invert_intrinsics", "dd3d_nms_finalize", "dd3d_bev_nms_aggregate", "dd3d_conv2d_smallc_supported", "dd3d_conv2d_smallc_bf16x3", "dd3d_rotate_iou_eval", "dd3d_d3_box_overlap", "dd3d_image_box_overlap", "dd3d_aligned_bilinear_scale", "dd3d_resize_bilinear_u8",
-    "dd3d_format_boxes3d", "dd3d_math_planes", "dd3d_split_planes", "dd3d_maxpool2x2_planes", "dd3d_maxpool2x2_planes_in", "dd3d_upsample2x_add_planes", "dd3d_ese_fused", "dd3d_stem_fused_f16x2", "dd3d_fold_range_flags", "dd3d_pack_readback",
+    "dd3d_format_boxes3d", "dd3d_math_planes", "dd3d_split_planes", "dd3d_maxpool2x2_planes", "dd3d_maxpool2x2_planes_in", "dd3d_upsample2x_add_planes", "dd3d_ese_fused", "dd3d_stem_fused_f16x2", "dd3d_stem_fused_keep_f16x2", "dd3d_fold_range_flags", "dd3d_pack_readback",
     "dd3d_kitti_tp_scores", "dd3d_kitti_pr_counts", "dd3d_nusc_center_match", "dd3d_loss_assign", "dd3d_loss_terms", "dd3d_loss_layout",
     "dd3d_dense_depth_loss", "dd3d_dense_depth_loss_layout", "dd3d_loss_backward", "dd3d_loss_grad_layout",
     "dd3d_dense_depth_loss_backward", "dd3d_dense_depth_grad_rows", "dd3d_dense_depth_grad_layout",
     "dd3d_predictor_wgrad", "dd3d_predictor_dgrad", "dd3d_predictor_grad_slices", "dd3d_pred_grad_layout",
     "dd3d_tower_wgrad", "dd3d_tower_dgrad", "dd3d_tower_grad_slices", "dd3d_tower_grad_layout",
     "dd3d_fpn_wgrad", "dd3d_fpn_dgrad", "dd3d_fpn_grad_slices", "dd3d_fpn_grad_layout",
-    "dd3d_backbone_wgrad", "dd3d_backbone_dgrad", "dd3d_backbone_grad_slices", "dd3d_maxpool2x2_backward", "dd3d_backbone_grad_layout"
+    "dd3d_backbone_wgrad", "dd3d_backbone_dgrad", "dd3d_backbone_grad_slices", "dd3d_maxpool2x2_backward", "dd3d_backbone_grad_layout",
+    "dd3d_stem_wgrad", "dd3d_stem_dgrad", "dd3d_stem_grad_slices", "dd3d_stem_grad_layout"
 ]
 
 
@@ -396,6 +430,7 @@ def lib():
     L.dd3d_conv2d_smallc_supported.argtypes = [C.c_int32] * 6
     L.dd3d_conv2d_smallc_bf16x3.argtypes = [C.POINTER(SmallcArgs), C.c_void_p]
     L.dd3d_stem_fused_f16x2.argtypes = [C.POINTER(StemArgs), C.c_void_p]
+    L.dd3d_stem_fused_keep_f16x2.argtypes = [C.POINTER(StemKeepArgs), C.c_void_p]
     L.dd3d_fold_range_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
     L.dd3d_pack_readback.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     L.dd3d_rotate_iou_eval.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p]
@@ -445,6 +480,11 @@ def lib():
     L.dd3d_backbone_grad_slices.restype = C.c_int64
     L.dd3d_maxpool2x2_backward.argtypes = [C.POINTER(PoolGradArgs), C.c_void_p]
     L.dd3d_backbone_grad_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_stem_wgrad.argtypes = [C.POINTER(StemGradArgs), C.c_void_p]
+    L.dd3d_stem_dgrad.argtypes = [C.POINTER(StemGradArgs), C.c_void_p]
+    L.dd3d_stem_grad_slices.argtypes = [C.POINTER(StemGradArgs)]
+    L.dd3d_stem_grad_slices.restype = C.c_int64
+    L.dd3d_stem_grad_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

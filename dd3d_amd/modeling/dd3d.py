@@ -119,20 +119,21 @@ class DD3D(nn.Module):
         self._evict_plans()
         return plan
 
-    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False):
+    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False, stem_grads=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
         `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
         backward behind it as well (parameter and tower-output gradients; implies `grads`); `tower_grads`: the plan that goes on through
         the head towers (their parameter gradients and the gradient at the FPN outputs; implies `pred_grads`); `fpn_grads`: the plan that
         goes on through the FPN (its parameter gradients and the gradient at the backbone's output features; implies `tower_grads`);
         `backbone_grads`: the plan that goes on through DLA-34's level5 .. level2 (their parameter gradients and the gradient at the stem's
-        output; implies `fpn_grads`)."""
+        output; implies `fpn_grads`); `stem_grads`: the plan that goes on through the stem (base_layer, level0, level1: their parameter
+        gradients and the gradients at base_layer's and level0's outputs; implies `backbone_grads`)."""
         from dd3d_amd.engine.losses import LossPlan
         key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + \
-            (("backbone_grads", ) if backbone_grads else ("fpn_grads", ) if fpn_grads else ("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
+            (("stem_grads", ) if stem_grads else ("backbone_grads", ) if backbone_grads else ("fpn_grads", ) if fpn_grads else ("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
         plan = self._plans.pop(key, None)
         if plan is None:
-            plan = LossPlan(self, B, Hp, Wp, backbone_grads=True) if backbone_grads else LossPlan(self, B, Hp, Wp, fpn_grads=True) if fpn_grads else LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
+            plan = LossPlan(self, B, Hp, Wp, stem_grads=True) if stem_grads else LossPlan(self, B, Hp, Wp, backbone_grads=True) if backbone_grads else LossPlan(self, B, Hp, Wp, fpn_grads=True) if fpn_grads else LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
                 LossPlan(self, B, Hp, Wp, grads=True) if grads else LossPlan(self, B, Hp, Wp)
             if self.use_graph:
                 plan.capture()
@@ -295,7 +296,8 @@ class DD3D(nn.Module):
 
     # ------------------------------------------------------------------ training losses (gradients: head maps and the predictor layer)
     @torch.no_grad()
-    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False):
+    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
+                       stem_grads=False):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
@@ -318,15 +320,22 @@ class DD3D(nn.Module):
         stay the FPN's contribution at those features), `grads` also holds backbone_level1 -- the gradient at the stem's stored output,
         (B, 32, Hp / 2, Wp / 2), not yet masked by that tensor's own ReLU -- and `param_grads` also every parameter of
         backbone.bottom_up.level2 .. level5 (the filters of tree*.conv1 / conv2, project and root.conv; a BN backbone's norm weights and
-        biases; a norm-less backbone's conv biases; FrozenBN, the released configs' norm, owns nothing).  The backward stops there: the
-        stem (base_layer, level0, level1) has none, and there is no optimiser, no batch-statistics norm and no model.train().  V2-99, the
-        Bottleneck DLA variants, force_generic_dla and the reduced arithmetic modes raise NotImplementedError."""
+        biases; a norm-less backbone's conv biases; FrozenBN, the released configs' norm, owns nothing).  With `stem_grads` the result has
+        the same form a last time and the backward goes on through the stem: everything `backbone_grads` returns, bit for bit, `grads`
+        also holds backbone_level0 and backbone_base_layer -- the gradients at level0's and base_layer's outputs, (B, 16, Hp, Wp), neither
+        masked by its tensor's own ReLU yet -- and `param_grads` also backbone.bottom_up.base_layer / level0.0 / level1.0 (.weight; a BN
+        backbone's .norm.weight / .norm.bias; a norm-less backbone's .bias): for DLA-34 its keys are then those of named_parameters().
+        The filter copies the backward reads are snapshots taken when the plan is built; there is no optimiser, no batch-statistics
+        norm and no model.train().  V2-99, the Bottleneck DLA variants, force_generic_dla and the reduced arithmetic modes raise
+        NotImplementedError."""
         from dd3d_amd.engine import relax_arithmetic
         gt = [x["instances"] for x in batched_inputs]
         while True:
+            backbone_grads = backbone_grads or stem_grads
             fpn_grads = fpn_grads or backbone_grads
             tower_grads = tower_grads or fpn_grads
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), backbone_grads=True) if backbone_grads else \
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), stem_grads=True) if stem_grads else \
+                self.get_loss_plan(*self.canvas_size(batched_inputs), backbone_grads=True) if backbone_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), fpn_grads=True) if fpn_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), tower_grads=True) if tower_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), pred_grads=True) if predictor_grads else \
@@ -354,6 +363,9 @@ class DD3D(nn.Module):
                 if backbone_grads:
                     l1, bparams = plan.backbone_grads()
                     towers, params = dict(towers, **l1), dict(params, **bparams)
+                if stem_grads:
+                    st, sparams = plan.stem_grads()
+                    towers, params = dict(towers, **st), dict(params, **sparams)
                 return losses, dict(plan.head_grads(), **towers), params
             return (losses, plan.head_grads()) if head_grads else losses
 

@@ -285,6 +285,19 @@ typedef struct dd3d_stem_args {  /* host memory; all pointers device */
   int32_t zero_count;
 } dd3d_stem_args;
 int dd3d_stem_fused_f16x2(const dd3d_stem_args* args, void* stream);
+/* The same launch for a plan that runs the stem's backward (dd3d_stem_wgrad / dd3d_stem_dgrad below): `stem` is dd3d_stem_args as above
+ * and produces the same bits in out / out_planes; each block also stores the part of its base_layer and level0 tiles it owns -- the
+ * canvas pixels [2 oh0, 2 oh0 + 16) x [2 ow0, 2 ow0 + 64) of its 8 x 32 level1 tile at (oh0, ow0), clipped to the canvas -- as f32 NHWC,
+ * [B][Hp][Wp][pitch], channels 0 .. 15: the decoded value (hi + lo) / plane_scale of the LDS planes, exactly what the next layer
+ * consumed.  Every pixel has one writer.  Rejected like dd3d_stem_fused_f16x2, and: a NULL or misaligned (16 bytes) keep pointer, a
+ * pitch below 16 or not a multiple of 4. */
+typedef struct dd3d_stem_keep_args {
+  dd3d_stem_args stem;
+  float* keep_base;
+  float* keep_level0;
+  int32_t keep_base_pitch, keep_level0_pitch;
+} dd3d_stem_keep_args;
+int dd3d_stem_fused_keep_f16x2(const dd3d_stem_keep_args* args, void* stream);
 int dd3d_conv2d_smallc_bf16x3(const dd3d_smallc_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -1080,6 +1093,60 @@ int dd3d_backbone_dgrad(const dd3d_backbone_grad_args* args, void* stream);
 int64_t dd3d_backbone_grad_slices(const dd3d_backbone_grad_args* args);
 int dd3d_maxpool2x2_backward(const dd3d_pool_grad_args* args, void* stream);
 int dd3d_backbone_grad_layout(int64_t* out, int32_t n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the DLA-34 stem's convolutions (csrc/stem_grads.hip): base_layer (7 x 7 on the normalised four-channel image), level0.0
+ * (3 x 3) and level1.0 (3 x 3, stride 2), each conv + folded norm + ReLU with ONE consumer.  The contract and the quantities are
+ * dd3d_backbone_wgrad's / dd3d_backbone_dgrad's above (gm, dw_level, dw, q, r, da, the norm read-out, H and W the INPUT's sizes, padding
+ * (k - 1) / 2, output size ceil(H / stride)) with these differences:
+ *   shapes   (ksize, stride, Cin, Cout) in {(7, 1, 4, 16), (3, 1, 16, 16), (3, 2, 16, 32)}; dd3d_stem_dgrad takes the two 3 x 3 only (the
+ *            image has no gradient).  The 7 x 7 reads four channels per pixel; dw's column of channel 3 is computed like the others.
+ *   operands x, g, da: f32 NHWC with pitches x_pitch, g_pitch, da_pitch (dgrad: g 16-byte aligned).  y: any DD3D_PG_ACT_* storage, always
+ *            present (every stem layer has a ReLU).
+ *   da       = sum_{n,ky,kx} scale[n] * gm * w alone: a stem tensor has one consumer, there is no `add` and no residual pair.
+ * Both are GEMMs on v_mfma_f32_16x16x4_f32 (exact f32 products, f32 accumulation).  The weight gradient: per-slice partials in `part` /
+ * `qpart`; a slice is dd3d_stem_grad_slices' run of units of up to DD3D_SG_UNIT output pixels of a row -- as many units as give about
+ * DD3D_SG_TARGET_SLICES slices, between DD3D_SG_MIN_UNITS_PER_SLICE and DD3D_SG_MAX_UNITS_PER_SLICE, more once the slab would pass
+ * DD3D_TG_SLAB_BYTES; inside a slice four runs of every fourth unit, added as (0 + 2) + (1 + 3); the slices are summed in slice order,
+ * 64 to a sub-sum.  The slicing depends on the shape alone.  wgrad_blocks: blocks of the weight gradient's main launch (0: one per slice;
+ * fewer: a block walks several slices); the result does not depend on it.  The input gradient: one chain per output word, (tap, n) order
+ * within the taps that reach it -- the stride-2 call visits the 4 / 2 / 2 / 1 taps of an input pixel's (row, column) parity only.
+ * One writer and a fixed order per sum: two runs agree bit for bit.  Every word of dw_level, dw, q, r (wgrad) and of the Cin channels of
+ * da (dgrad) is written; nothing beyond them and the slab rows in use.  dd3d_stem_wgrad: three launches; dd3d_stem_dgrad: one.  Safe
+ * under stream capture.  dd3d_stem_grad_slices: host only, reads B, H, W, Cin, Cout, ksize, stride.  dd3d_stem_grad_layout: sizeof and
+ * field offsets.
+ * Rejected (-1, dd3d_last_error starts with the entry point's name): any other (ksize, stride, Cin, Cout), the 7 x 7 in dgrad, pitches
+ *   not a multiple of 4 or too small, an unknown y storage, null pointers, a misaligned g (dgrad), too few slab rows, a negative
+ *   wgrad_blocks, more than DD3D_BG_MAX_PIXELS input pixels.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_SG_UNIT 64
+#define DD3D_SG_TARGET_SLICES 512           /* two blocks per CU of 256; not measured */
+#define DD3D_SG_MIN_UNITS_PER_SLICE 8
+#define DD3D_SG_MAX_UNITS_PER_SLICE 64
+typedef struct dd3d_stem_grad_args {        /* host memory; every pointer is device memory */
+  const float* x;                           /* convolution input [B][H][W][x_pitch] (wgrad) */
+  const void* y;                            /* stored output behind the ReLU [B][Ho][Wo], storage y_mode */
+  const float* g;                           /* gradient at the output: [B][Ho][Wo][g_pitch] */
+  const float* w;                           /* [Cout][ksize][ksize][Cin] */
+  const float* scale;                       /* [Cout] */
+  float* da;                                /* [B][H][W][da_pitch] (dgrad) */
+  float* part;                              /* scratch [n_slices][Cout][ksize * ksize * Cin] */
+  float* qpart;                             /* scratch [n_slices][Cout] */
+  float* dw_level;                          /* [Cout][ksize * ksize * Cin] */
+  float* dw;                                /* [Cout][ksize * ksize * Cin] */
+  float* q;                                 /* [Cout] */
+  float* r;                                 /* [Cout] */
+  int32_t B, H, W, Cin, Cout, ksize, stride;
+  int32_t x_pitch, g_pitch, da_pitch;
+  int32_t y_mode, y_pitch;                  /* DD3D_PG_ACT_*; floats per pixel (DD3D_PG_ACT_F32) */
+  int32_t n_slices;                         /* rows of part / qpart */
+  int32_t wgrad_blocks;
+  float y_plane_scale;                      /* DD3D_PG_ACT_F16X2 */
+} dd3d_stem_grad_args;
+int dd3d_stem_wgrad(const dd3d_stem_grad_args* args, void* stream);
+int dd3d_stem_dgrad(const dd3d_stem_grad_args* args, void* stream);
+int64_t dd3d_stem_grad_slices(const dd3d_stem_grad_args* args);
+int dd3d_stem_grad_layout(int64_t* out, int32_t n);
 
 #ifdef __cplusplus
 }
