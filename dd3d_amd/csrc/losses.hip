@@ -23,6 +23,8 @@ DD3D_NOTE_BUILD_FLAGS
 namespace dd3d {
 
 // ------------------------------------------------------------------------------------------------ assignment
+__global__ void loss_clear_flags_kernel(int32_t* flags) { flags[0] = 0; }
+
 __global__ __launch_bounds__(LT) void loss_assign_kernel(const LossK P) {
   const dd3d_loss_args& a = P.a;
   const int b = blockIdx.y;
@@ -254,7 +256,12 @@ extern "C" int dd3d_loss_assign(const dd3d_loss_args* args, void* stream) {
   for (int l = 0; l < args->num_levels; ++l) any3d |= args->box3d[l] != nullptr;
   DD3D_REQUIRE(!any3d || (args->inv_K && args->canon_sizes), "dd3d_loss_assign: box3d maps need inv_K and canon_sizes");
   const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(args->flags, 0, sizeof(int32_t), s) != hipSuccess) return check_launch("dd3d_loss_assign memset");
+  // The trigger word is cleared by a kernel, not by hipMemsetAsync: captured into a plan's hipGraph, the memset node of the larger
+  // training graphs was replayed with other fill bytes than 0 after a dozen replays (0x20202020, 0xF0F0F0F0 read back on the MI355X),
+  // which switched every positive of those steps to the renormalised decode (tests/test_loss_plan_history_gpu.py).
+  hipLaunchKernelGGL(loss_clear_flags_kernel, dim3(1), dim3(1), 0, s, args->flags);
+  int e = check_launch("loss_clear_flags_kernel");
+  if (e != DD3D_OK) return e;
   const int nloc = args->loc_off[args->num_levels];
   hipLaunchKernelGGL(loss_assign_kernel, dim3((unsigned)ceil_div(nloc, LT), (unsigned)args->B), dim3(LT), 0, s, LossK{*args});
   return check_launch("loss_assign_kernel");

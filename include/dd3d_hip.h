@@ -635,7 +635,9 @@ int dd3d_nusc_center_match(const dd3d_nusc_match_args* args, int32_t* match, voi
  *   target_inds (-1 for an image without GT), box2d_reg [N][4], ctr_target [N] (0 off the positives), box3d_t [N][19]
  *   (quat 4, proj_ctr 2, depth 1, size 3, K^-1 9) and, when `attributes` is set, attributes [N] / speeds [N].  With box3d head maps
  *   it also ORs into flags[0] whether an allocentric decode of a positive is off unit norm (the batch-wide renormalisation of
- *   geometry.py:48-53, which the loss stage needs before it can decode).
+ *   geometry.py:48-53, which the loss stage needs before it can decode);
+ *   a one-thread launch in front clears flags[0] (a kernel, not hipMemsetAsync: a captured memset node did not keep its fill bytes
+ *   over the replays of the larger training graphs).
  * dd3d_loss_terms: one thread per target reads the head maps (layouts of dd3d_select_args), writes per-block partial sums of
  *   DD3D_LOSS_TERMS terms to `partials` (>= ceil(N / 256) rows), then one single-block launch sums them in a fixed order and writes
  *   out[DD3D_LOSS_OUT] and num_pos[0].  No float atomics: the result is the same bit for bit on every run.

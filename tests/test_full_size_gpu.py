@@ -14,6 +14,7 @@ import torch
 
 from tests.test_forward_gpu import MARGIN_EPS, REL_TOL, _check_final, _check_head_maps, _nusc_check, _oracle
 from tests.util import bundle, candidate_margins, gpu_model, max_abs, oracle_heads_to_plan, rel_err
+from tests.util import scaled_between as _scaled_between  # (shared with tests/test_loss_plan_history_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -309,17 +310,6 @@ def test_half_range_guard_of_the_default_arithmetic(hiplib, kitti_dla34, monkeyp
     ref, _ = _oracle(cfg, sd, inputs)
     assert len(out[0]["instances"]) == len(ref[0]["scores"]) > 0
     assert rel_err(out[0]["instances"].pred_boxes3d.depth, ref[0]["pred_boxes3d"]["depth"]) < REL_TOL
-
-
-def _scaled_between(sd, bn_a, bn_b, factor):
-    """The same network function with the activation BETWEEN norm `bn_a` (+ ReLU + conv) and norm `bn_b` multiplied by `factor`:
-    bn_a's affine is scaled, bn_b's running statistics absorb it (ReLU and the convolution are positively homogeneous)."""
-    sd = {k: v.clone() for k, v in sd.items()}
-    sd[bn_a + ".weight"] *= factor
-    sd[bn_a + ".bias"] *= factor
-    sd[bn_b + ".running_mean"] *= factor
-    sd[bn_b + ".running_var"] *= factor * factor
-    return sd
 
 
 def test_half_range_guard_with_realistic_statistics(hiplib, kitti_dla34, monkeypatch):

@@ -51,20 +51,15 @@ def _compare(what, rows):
         assert gmax > 0.0, (what, stage, fam)
         assert dev <= bar, (what, stage, fam, dev, bar, d32, gmax)
     print(f"[whole_model_grads] {what}: the worst family uses {worst:.2f} of the factor 8")
+    return worst
 
 
-@pytest.mark.parametrize("name", list(WO.CASES))
-def test_composed_backward_is_the_whole_model_gradient(hiplib, name):
-    from tests.test_loss_grads_gpu import _model
+def compare_with_whole_model_oracle(name, case, model, cpu, inputs, gt):
+    """The body of the comparison, shared with tests/test_loss_plan_history_gpu.py (plane scale 4, reached through the range guard):
+    `model` on the GPU and `cpu` carry the same state dict, `inputs` carry `gt` as their instances; `case`: an entry like those of
+    WO.CASES (`ref` keys the cached natural float64 forward; `math` / `act_scale`: what the plan's stored activations must show).
+    Returns (the worst use of the factor 8, losses, grads, param_grads of the call)."""
     from tests.test_losses_gpu import _close
-    case = WO.CASES[name]
-    model = _model(case["exp"], case["weights"], case["overrides"])
-    model.math, model.act_scale = case["math"], case["act_scale"]
-    cpu = GC.cpu_model(case["exp"], case["overrides"])
-    cpu.load_state_dict({k: v.cpu() for k, v in model.state_dict().items()})
-    inputs, gt = WO.case_inputs(case, cpu)
-    for x, g in zip(inputs, gt):
-        x["instances"] = g
     through = {case["grads"]: True}  # backbone_grads, or fpn_grads for V2-99, whose backward stops at the backbone's output features
     losses, grads, params = model.compute_losses(inputs, **through)
     plan = model.get_loss_plan(*model.canvas_size(inputs), **through)
@@ -108,13 +103,29 @@ def test_composed_backward_is_the_whole_model_gradient(hiplib, name):
     for k in a64:
         tf.setdefault(WO.tensor_family_of(k), []).append(k)
     rows += [("tensors", fam, [grads[k] for k in ks], [a64[k] for k in ks], [a32[k] for k in ks]) for fam, ks in sorted(tf.items())]
-    _compare(name, rows)
+    worst = _compare(name, rows)
 
     # the loss dict against the float32 oracle's own forward
     ref_losses = {k: e32["losses"][k] for k in losses}
     for k in losses:
         print(f"[whole_model_grads] {name} {k}: {float(losses[k]):.7g} oracle {float(ref_losses[k]):.7g}")
     _close({k: v.cpu() for k, v in losses.items()}, ref_losses, LOSS_REL[case["ds"]])
+    return worst, losses, grads, params
+
+
+@pytest.mark.parametrize("name", list(WO.CASES))
+def test_composed_backward_is_the_whole_model_gradient(hiplib, name):
+    from tests.test_loss_grads_gpu import _model
+    case = WO.CASES[name]
+    model = _model(case["exp"], case["weights"], case["overrides"])
+    model.math, model.act_scale = case["math"], case["act_scale"]
+    cpu = GC.cpu_model(case["exp"], case["overrides"])
+    cpu.load_state_dict({k: v.cpu() for k, v in model.state_dict().items()})
+    inputs, gt = WO.case_inputs(case, cpu)
+    for x, g in zip(inputs, gt):
+        x["instances"] = g
+    through = {case["grads"]: True}
+    _, losses, grads, params = compare_with_whole_model_oracle(name, case, model, cpu, inputs, gt)
 
     # a second call is bit-equal; the captured graph equals launch-by-launch execution
     l2, g2, p2 = model.compute_losses(inputs, **through)

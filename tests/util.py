@@ -49,6 +49,17 @@ def gpu_model(cfg, sd, use_graph=True, math=None):
     return model
 
 
+def scaled_between(sd, bn_a, bn_b, factor):
+    """The same network function with the activation BETWEEN norm `bn_a` (+ ReLU + conv) and norm `bn_b` multiplied by `factor`:
+    bn_a's affine is scaled, bn_b's running statistics absorb it (ReLU and the convolution are positively homogeneous)."""
+    sd = {k: v.clone() for k, v in sd.items()}
+    sd[bn_a + ".weight"] *= factor
+    sd[bn_a + ".bias"] *= factor
+    sd[bn_b + ".running_mean"] *= factor
+    sd[bn_b + ".running_var"] *= factor * factor
+    return sd
+
+
 def oracle_heads_to_plan(plan, st, num_classes):
     """Overwrite the plan's head-map buffers with the oracle's head maps (NCHW -> fused NHWC layout)."""
     for l in range(len(st["logits"])):
