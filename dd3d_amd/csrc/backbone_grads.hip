@@ -353,14 +353,13 @@ static int check_mode(const char* who, const char* nm, int mode, int pitch, int 
 }
 
 // what the tiling depends on: the geometry, the channel counts and the convolution's form
-static int check_backbone_shape(const dd3d_backbone_grad_args* a, const char* who) {
+static int check_backbone_shape(const dd3d_backbone_grad_args* a, const char* who, int max_cin = DD3D_BG_MAX_CIN, int max_cout = DD3D_BG_MAX_COUT) {
   DD3D_REQUIRE(a != nullptr, "%s: null args", who);
   DD3D_REQUIRE(a->B >= 1 && a->H >= 1 && a->W >= 1, "%s: B = %d, %d x %d", who, a->B, a->H, a->W);
   DD3D_REQUIRE(a->ksize == 1 || a->ksize == 3, "%s: ksize = %d (1 or 3)", who, a->ksize);
   DD3D_REQUIRE(a->stride == 1 || a->stride == 2, "%s: stride = %d (1 or 2)", who, a->stride);
-  DD3D_REQUIRE(a->Cin >= 32 && a->Cin % 32 == 0 && a->Cin <= DD3D_BG_MAX_CIN, "%s: Cin = %d is not a multiple of 32 up to %d", who, a->Cin, DD3D_BG_MAX_CIN);
-  DD3D_REQUIRE(a->Cout >= 32 && a->Cout % 32 == 0 && a->Cout <= DD3D_BG_MAX_COUT, "%s: Cout = %d is not a multiple of 32 up to %d", who, a->Cout,
-               DD3D_BG_MAX_COUT);
+  DD3D_REQUIRE(a->Cin >= 32 && a->Cin % 32 == 0 && a->Cin <= max_cin, "%s: Cin = %d is not a multiple of 32 up to %d", who, a->Cin, max_cin);
+  DD3D_REQUIRE(a->Cout >= 32 && a->Cout % 32 == 0 && a->Cout <= max_cout, "%s: Cout = %d is not a multiple of 32 up to %d", who, a->Cout, max_cout);
   DD3D_REQUIRE(a->dgrad_rows == 0 || a->dgrad_rows == 2 || a->dgrad_rows == 4 || a->dgrad_rows == 8, "%s: dgrad_rows = %d (0, 2, 4 or 8)", who, a->dgrad_rows);
   DD3D_REQUIRE(a->dgrad_group == 0 || a->dgrad_group == 128 || a->dgrad_group == 256, "%s: dgrad_group = %d (0, 128 or 256)", who, a->dgrad_group);
   // (every pixel and word index is a long; what is an int is a count of pixels, units or blocks: below 2^26 pixels all of them fit)
@@ -368,8 +367,9 @@ static int check_backbone_shape(const dd3d_backbone_grad_args* a, const char* wh
   return DD3D_OK;
 }
 
-static int check_backbone_args(const dd3d_backbone_grad_args* a, const char* who, bool wgrad) {
-  int rc = check_backbone_shape(a, who);
+static int check_backbone_args(const dd3d_backbone_grad_args* a, const char* who, bool wgrad, int max_cin = DD3D_BG_MAX_CIN,
+                               int max_cout = DD3D_BG_MAX_COUT) {
+  int rc = check_backbone_shape(a, who, max_cin, max_cout);
   if (rc != DD3D_OK) return rc;
   DD3D_REQUIRE(a->g_pitch % 4 == 0 && a->g_pitch >= a->Cout, "%s: g_pitch = %d must be a multiple of 4 and hold %d channels", who, a->g_pitch, a->Cout);
   DD3D_REQUIRE(a->g && a->w && a->scale, "%s: no gradient / filter / scale", who);
@@ -416,14 +416,13 @@ extern "C" int64_t dd3d_backbone_grad_slices(const dd3d_backbone_grad_args* args
   return k.nslices;
 }
 
-extern "C" int dd3d_backbone_wgrad(const dd3d_backbone_grad_args* args, void* stream) {
-  using namespace dd3d;
-  const int rc = check_backbone_args(args, "dd3d_backbone_wgrad", true);
-  if (rc != DD3D_OK) return rc;
-  DD3D_REQUIRE(args->dw_level && args->dw && args->q && args->r, "dd3d_backbone_wgrad: null output");
+namespace dd3d {
+// the three launches of a weight gradient and the one of an input gradient, behind the argument checks of their entry points
+static int run_wgrad(const dd3d_backbone_grad_args* args, const char* who, void* stream) {
+  DD3D_REQUIRE(args->dw_level && args->dw && args->q && args->r, "%s: null output", who);
   BackK k;
   plan_backbone(*args, k);
-  DD3D_REQUIRE(args->part && args->qpart && args->n_slices >= k.nslices, "dd3d_backbone_wgrad: part / qpart (%d slices for %d)", args->n_slices, k.nslices);
+  DD3D_REQUIRE(args->part && args->qpart && args->n_slices >= k.nslices, "%s: part / qpart (%d slices for %d)", who, args->n_slices, k.nslices);
   const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int KK = args->ksize * args->ksize * args->Cin;
   const dim3 grid((unsigned)k.nslices, (unsigned)(args->Cin / 32), (unsigned)ceil_div(args->Cout, BG_TN));
@@ -439,16 +438,53 @@ extern "C" int dd3d_backbone_wgrad(const dd3d_backbone_grad_args* args, void* st
   return check_launch("bb_rsum_kernel");
 }
 
-extern "C" int dd3d_backbone_dgrad(const dd3d_backbone_grad_args* args, void* stream) {
-  using namespace dd3d;
-  const int rc = check_backbone_args(args, "dd3d_backbone_dgrad", false);
-  if (rc != DD3D_OK) return rc;
+static int run_dgrad(const dd3d_backbone_grad_args* args, void* stream) {
   BackK k;
   plan_backbone(*args, k);
   const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (args->ksize == 3) launch_bb_dgrad<3>(k, s);
   else launch_bb_dgrad<1>(k, s);
   return check_launch("bb_dgrad_kernel");
+}
+}  // namespace dd3d
+
+extern "C" int dd3d_backbone_wgrad(const dd3d_backbone_grad_args* args, void* stream) {
+  using namespace dd3d;
+  const int rc = check_backbone_args(args, "dd3d_backbone_wgrad", true);
+  if (rc != DD3D_OK) return rc;
+  return run_wgrad(args, "dd3d_backbone_wgrad", stream);
+}
+
+extern "C" int dd3d_backbone_dgrad(const dd3d_backbone_grad_args* args, void* stream) {
+  using namespace dd3d;
+  const int rc = check_backbone_args(args, "dd3d_backbone_dgrad", false);
+  if (rc != DD3D_OK) return rc;
+  return run_dgrad(args, stream);
+}
+
+// ---- the VoVNet backbone's convolutions (include/dd3d_hip.h, the VoVNet section): the same kernels under wider limits.  Nothing in the
+// kernels' indexing depends on the DLA limits: every word index is a long, the LDS tiles are sized by the unit and the 32-channel chunk
+// alone, and the grids grow with Cin / 32 and Cout / 128.
+extern "C" int64_t dd3d_vovnet_conv_grad_slices(const dd3d_backbone_grad_args* args) {
+  using namespace dd3d;
+  if (check_backbone_shape(args, "dd3d_vovnet_conv_grad_slices", DD3D_VG_MAX_CIN, DD3D_VG_MAX_COUT) != DD3D_OK) return -1;
+  BackK k;
+  plan_backbone(*args, k);
+  return k.nslices;
+}
+
+extern "C" int dd3d_vovnet_conv_wgrad(const dd3d_backbone_grad_args* args, void* stream) {
+  using namespace dd3d;
+  const int rc = check_backbone_args(args, "dd3d_vovnet_conv_wgrad", true, DD3D_VG_MAX_CIN, DD3D_VG_MAX_COUT);
+  if (rc != DD3D_OK) return rc;
+  return run_wgrad(args, "dd3d_vovnet_conv_wgrad", stream);
+}
+
+extern "C" int dd3d_vovnet_conv_dgrad(const dd3d_backbone_grad_args* args, void* stream) {
+  using namespace dd3d;
+  const int rc = check_backbone_args(args, "dd3d_vovnet_conv_dgrad", false, DD3D_VG_MAX_CIN, DD3D_VG_MAX_COUT);
+  if (rc != DD3D_OK) return rc;
+  return run_dgrad(args, stream);
 }
 
 extern "C" int dd3d_maxpool2x2_backward(const dd3d_pool_grad_args* a, void* stream) {

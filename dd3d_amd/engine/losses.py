@@ -4,7 +4,8 @@ layer's parameters and the tower outputs it reads (csrc/predictor_grads.hip), an
 their parameters and the FPN outputs (csrc/tower_grads.hip), and one stage further through the FPN to its parameters and the backbone's
 output features (csrc/fpn_grads.hip), and one stage further again through the DLA-34 backbone's level5 .. level2 to their parameters
 and the stem's output (csrc/backbone_grads.hip), and last through the stem -- base_layer, level0, level1 -- to its parameters
-(csrc/stem_grads.hip).  There is no optimiser, batch-statistics norm or model.train().
+(csrc/stem_grads.hip); for the VoVNet-V2 backbones, behind the FPN through stage5 .. stage2, stem_3 and stem_2 (csrc/vovnet_grads.hip and
+the wide entry points of csrc/backbone_grads.hip).  There is no optimiser, batch-statistics norm or model.train().
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -629,6 +630,106 @@ class StemConvGrads:
         return all(bool((t[n:] == fill).all()) for t, n in self._raw)
 
 
+class VovnetConvGrads(BackboneConvGrads):
+    """BackboneConvGrads through dd3d_vovnet_conv_wgrad / dd3d_vovnet_conv_dgrad: the same call and kernels under the limits
+    hip.VG_MAX_CIN / hip.VG_MAX_COUT."""
+    def launch(self, lib, st):
+        if self.with_wgrad:
+            hip.check(lib.dd3d_vovnet_conv_wgrad(C.byref(self.args), st), "vovnet_conv_wgrad")
+        if self.with_dgrad:
+            hip.check(lib.dd3d_vovnet_conv_dgrad(C.byref(self.args), st), "vovnet_conv_dgrad")
+
+
+class SumGrads:
+    """One dd3d_vovnet_add launch: `da` [B, H, W, C] = a + b, two f32 NHWC gradients of that shape (slices may be given).  `da` is
+    allocated here (filled with `fill`, followed by `guard` words)."""
+    def __init__(self, device, a, b, fill=0.0, guard=0):
+        assert tuple(a.shape) == tuple(b.shape) and a.dim() == 4 and a.stride(-1) == 1 and b.stride(-1) == 1, (tuple(a.shape), tuple(b.shape))
+        self.keep = (a, b)
+        numel = a.numel()
+        t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
+        self._raw = [(t, numel)]
+        self.da = t[:numel].view(*a.shape)
+        pitch = lambda v: int(v.stride(-2)) if v.shape[-2] > 1 or v.stride(-2) >= v.shape[-1] else int(v.shape[-1])
+        self.call = (a.data_ptr(), b.data_ptr(), self.da.data_ptr(), int(numel // a.shape[-1]), int(a.shape[-1]), pitch(a), pitch(b), int(a.shape[-1]))
+
+    def launch(self, lib, st):
+        hip.check(lib.dd3d_vovnet_add(*self.call, st), "vovnet_add")
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
+class EseGrads:
+    """Buffers and dd3d_ese_grad_args of one eSE gate's backward (csrc/vovnet_grads.hip): `xt` the binding of the stored pre-eSE tensor
+    ([B, H, W, C]), `g` the gradient at the module output ([B, H, W, C], a slice may be given), `fc_w` [C, C] and `fc_b` [C] on the
+    device.  Outputs are allocated here, filled with `fill` and followed by `guard` words of it: g_xt [B, H, W, C] (not masked by xt's own
+    ReLU), d_fc_w [C, C], d_fc_b [C], and the per-image vectors m, z, s, dz, u [B, C]."""
+    def __init__(self, device, B, H, W, Cc, xt, g, fc_w, fc_b, rsplit=None, fill=0.0, guard=0):
+        self.B, self.H, self.W, self.C = B, int(H), int(W), int(Cc)
+        self.keep = (g, fc_w, fc_b)
+        self._raw = []
+
+        def out(*shape):
+            numel = int(np.prod(shape))
+            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
+            self._raw.append((t, numel))
+            return t[:numel].view(*shape)
+
+        HW = self.H * self.W
+        self.rsplit = hip.ese_grad_rsplit(HW) if rsplit is None else int(rsplit)
+        assert tuple(g.shape) == (B, self.H, self.W, self.C) and g.stride(-1) == 1, (tuple(g.shape), (B, self.H, self.W, self.C))
+        assert tuple(fc_w.shape) == (self.C, self.C) and tuple(fc_b.shape) == (self.C, ) and fc_w.is_contiguous()
+        self.part = out(B, self.rsplit, 2, self.C)
+        self.m, self.z, self.s, self.dz, self.u = (out(B, self.C) for _ in range(5))
+        self.g_xt, self.d_fc_w, self.d_fc_b = out(B, self.H, self.W, self.C), out(self.C, self.C), out(self.C)
+        self.da = self.g_xt
+        a = hip.EseGradArgs()
+        a.xt, a.xt_mode, a.xt_pitch, a.xt_plane_scale = xt[1] or None, int(xt[0]), int(xt[2]), float(xt[3])
+        a.g, a.g_pitch = g.data_ptr(), int(g.stride(-2)) if g.shape[-2] > 1 or g.stride(-2) >= g.shape[-1] else int(g.shape[-1])
+        a.fc_w, a.fc_b = fc_w.data_ptr(), fc_b.data_ptr()
+        a.part, a.m, a.z, a.s, a.dz, a.u = (t.data_ptr() for t in (self.part, self.m, self.z, self.s, self.dz, self.u))
+        a.g_xt, a.gxt_pitch, a.d_fc_w, a.d_fc_b = self.g_xt.data_ptr(), self.C, self.d_fc_w.data_ptr(), self.d_fc_b.data_ptr()
+        a.B, a.HW, a.C, a.rsplit = int(B), HW, self.C, self.rsplit
+        self.args = a
+
+    def launch(self, lib, st):
+        hip.check(lib.dd3d_ese_backward(C.byref(self.args), st), "ese_backward")
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
+class Pool3Grads:
+    """Buffers and dd3d_pool3_grad_args of one MaxPool2d(3, 2, ceil_mode=True) backward: `x` the binding of the pool's stored input
+    ([B, H, W, C]), `g` the gradient at the pooled tensor ([B, pool3_out(H), pool3_out(W), C], a slice may be given), `add` [B, H, W, C] or
+    None.  `da` is allocated here (filled with `fill`, followed by `guard` words)."""
+    def __init__(self, device, B, H, W, Cc, x, g, add=None, fill=0.0, guard=0):
+        self.B, self.H, self.W, self.C = B, int(H), int(W), int(Cc)
+        self.Ho, self.Wo = hip.pool3_out(self.H), hip.pool3_out(self.W)
+        self.keep = (g, add)
+        numel = B * self.H * self.W * self.C
+        t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
+        self._raw = [(t, numel)]
+        self.da = t[:numel].view(B, self.H, self.W, self.C)
+        pitch = lambda v: int(v.stride(-2)) if v.shape[-2] > 1 or v.stride(-2) >= v.shape[-1] else int(v.shape[-1])
+        assert tuple(g.shape) == (B, self.Ho, self.Wo, self.C) and g.stride(-1) == 1, (tuple(g.shape), (B, self.Ho, self.Wo, self.C))
+        a = hip.Pool3GradArgs()
+        a.x, a.g, a.g_pitch, a.da, a.da_pitch = x[1] or None, g.data_ptr(), pitch(g), self.da.data_ptr(), self.C
+        a.B, a.H, a.W, a.C = int(B), self.H, self.W, self.C
+        a.x_mode, a.x_pitch, a.x_plane_scale = int(x[0]), int(x[2]), float(x[3])
+        if add is not None:
+            assert tuple(add.shape) == (B, self.H, self.W, self.C) and add.stride(-1) == 1
+            a.add, a.add_pitch = add.data_ptr(), pitch(add)
+        self.args = a
+
+    def launch(self, lib, st):
+        hip.check(lib.dd3d_maxpool3x3s2_ceil_backward(C.byref(self.args), st), "maxpool3x3s2_ceil_backward")
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
 def slice_binding(bind, c0, npix):
     """The binding (mode, address, pitch, plane scale) of the channel slice that starts at channel `c0` of a stored buffer with `npix`
     pixels: f32 moves the pointer by channels, split planes by whole 32-channel chunk images (f16x2: 128, bf16x3: 192 bytes a pixel)."""
@@ -786,6 +887,162 @@ def dla_param_grads(named, layers, prefix=""):
     return params
 
 
+def check_vovnet_backward(vov, model=None):
+    """NotImplementedError naming what the VoVNet backward does not cover (it covers BackboneLowering._vovnet for the specs whose channel
+    counts are multiples of 32: V-19-eSE, V-39-eSE, V-57-eSE, V-99-eSE)."""
+    from dd3d_amd.modeling.vovnet import VoVNet
+    if not isinstance(vov, VoVNet):
+        raise NotImplementedError(f"vovnet_grads covers the VoVNet-V2 backbones; {type(vov).__name__} has its own backward: use stem_grads=True")
+    if any(dw for _, _, dw in vov.stem_seqs):
+        raise NotImplementedError("vovnet_grads: the depthwise specs (V-19-dw-eSE, V-19-slim-dw-eSE) have no backward for their depthwise 3x3 layers")
+    for sname in vov.stage_names:
+        for mname, m in getattr(vov, sname).named_children():
+            if m.depthwise or m.conv_reduction is not None:
+                raise NotImplementedError(f"vovnet_grads: {sname}.{mname} is depthwise; the depthwise 3x3 layers and conv_reduction have no backward")
+            for what, ch in (("in_ch", m.in_ch), ("stage_ch", m.stage_ch), ("concat_ch", m.concat_ch)):
+                if ch % 32:
+                    raise NotImplementedError(f"vovnet_grads: {sname}.{mname}.{what} = {ch} is not a multiple of 32 (the slim specs): the gradient "
+                                              "kernels have no zero-padded channel handling")
+
+
+def _vovnet_geometry(vov, H1, W1):
+    """{stage name: (H, W) of its tensors} from the size H1 x W1 of stem_1's output."""
+    H, W = (H1 + 1) // 2, (W1 + 1) // 2  # stem_3: 3x3, stride 2, padding 1
+    hw = {}
+    for sname in vov.stage_names:
+        if getattr(vov, sname).has_pool:
+            H, W = hip.pool3_out(H), hip.pool3_out(W)
+        hw[sname] = (H, W)
+    return hw
+
+
+def _vovnet_conv_calls(vov, H1, W1):
+    """(ksize, stride, input H, W, Cin, Cout) of every convolution of the VoVNet backward; H1 x W1: stem_1's output."""
+    from dd3d_amd.modeling.vovnet import seq_conv
+    stem = [getattr(vov.stem, c) for c, _, _ in vov.stem_seqs]
+    calls = [(3, int(cv.stride), H1, W1, int(cv.weight.shape[1]), int(cv.weight.shape[0])) for cv in stem[1:]]
+    hw = _vovnet_geometry(vov, H1, W1)
+    for sname in vov.stage_names:
+        H, W = hw[sname]
+        for _, m in getattr(vov, sname).named_children():
+            cin = m.in_ch
+            for layer in m.layers:
+                calls.append((3, 1, H, W, cin, m.stage_ch))
+                cin = m.stage_ch
+            calls.append((1, 1, H, W, int(seq_conv(m.concat).weight.shape[1]), m.concat_ch))
+    return calls
+
+
+def vovnet_slab_words(B, vov, H1, W1):
+    """Floats of (part, qpart) the largest weight-gradient call of the VoVNet backward needs; H1 x W1: stem_1's output."""
+    rows = qrows = 0
+    for k, s, h, w_, ci, co in _vovnet_conv_calls(vov, H1, W1):
+        n = hip.backbone_grad_slices(B, h, w_, ci, co, k, s)
+        rows, qrows = max(rows, n * co * k * k * ci), max(qrows, n * co)
+    return rows, qrows
+
+
+def vovnet_backward(device, B, vov, G, acts, vec, slab=None, fill=0.0, guard=0, stages=None, stem=True):
+    """The calls of the VoVNet-V2 backward in their order, the last stage down to stem_2 (include/dd3d_hip.h states the mathematics).  Per
+    OSA module, last to first: eSE, the concat 1x1 (weight gradient, then the input gradient over the whole concat width into one D_cat),
+    layers n-1 .. 1 (layer i's incoming gradient is D_cat[slice i] + the input gradient of layer i+1, masked by the stored concat-buffer
+    slice while staged), under `identity` the module input's sum T = D_cat[x] + G_out (one elementwise launch), layer 0 (its input
+    gradient adds T, or D_cat[x] without the identity: (D_cat[x] + G_out) + dgrad).
+    Between stages the 3x3 pool backward, adding the FPN's gradient at the pool's input; after stage2 stem_3 (stride 2) and stem_2.
+
+    `G`: {stage<n>: [B, h, w, C] gradient the FPN sends to a stage output}; the last stage's is required; `acts`: {name of a stored buffer
+    of BackboneLowering._vovnet (<stage>.<module>.cat, <stage>.<module>.xt, <stage>.out, stem.0, stem.1): ((mode, address, pitch, plane
+    scale) of the WHOLE buffer, H, W, C)}; `vec`: host vector -> device; `stages`: a run of consecutive stage names (default: all); `stem`:
+    go on through stem_3 and stem_2 when the run starts at stage2.  Returns ({key: EseGrads, VovnetConvGrads, SumGrads or Pool3Grads}, the gradient
+    at the tensor the chain ends at: stem_1's stored output, not masked by its own ReLU, or the first stage's input); a convolution's
+    layer carries its module as `conv`, its norm as `norm` and what it reads as `src` = {operand: (buffer name, first channel, channels)}."""
+    from dd3d_amd.layers import fold_norm
+    from dd3d_amd.modeling.vovnet import seq_conv, seq_norm
+    check_vovnet_backward(vov)
+    layers, common = OrderedDict(), dict(fill=fill, guard=guard)
+
+    def bind(ref):
+        key, c0, _ = ref
+        b, h, w_, _ = acts[key]
+        return slice_binding(b, c0, B * h * w_)
+
+    def conv(key, mod, norm, x, y, g, add=None):
+        k, cin, cout, stride = int(mod.weight.shape[-1]), int(mod.weight.shape[1]), int(mod.weight.shape[0]), int(mod.stride)
+        assert x[2] == cin and y[2] == cout, (key, x, y)
+        H, W = acts[x[0]][1], acts[x[0]][2]
+        w = mod.weight.detach().float().permute(0, 2, 3, 1).contiguous().to(device)
+        lay = VovnetConvGrads(device, B, H, W, cin, cout, k, stride, bind(x), bind(y), g, w, vec(fold_norm(mod, norm)[0]), add=add, slab=slab,
+                              **common)
+        lay.conv, lay.norm, lay.src = mod, norm, dict(x=x, y=y)
+        layers[key] = lay
+        return lay.da
+
+    names = list(stages or vov.stage_names)
+    g = G[names[-1]]
+    for si in reversed(range(len(names))):
+        sname = names[si]
+        stage = getattr(vov, sname)
+        mods = list(stage.named_children())
+        for mname, m in reversed(mods):
+            cat, xt = f"{sname}.{mname}.cat", f"{sname}.{mname}.xt"
+            n, pin, pst, pcc = len(m.layers), m.in_ch, m.stage_ch, m.concat_ch
+            H, W, catC = acts[cat][1:]
+            assert catC == pin + n * pst and acts[xt][1:] == (H, W, pcc), (cat, acts[cat][1:], acts[xt][1:])
+            fc = m.ese.fc
+            ese = EseGrads(device, B, H, W, pcc, bind((xt, 0, pcc)), g, vec(fc.weight.reshape(pcc, pcc)), vec(fc.bias), **common)
+            ese.fc, ese.src = fc, dict(xt=(xt, 0, pcc))
+            layers[f"{sname}.{mname}.ese"] = ese
+            Dcat = conv(f"{sname}.{mname}.concat", seq_conv(m.concat), seq_norm(m.concat), (cat, 0, catC), (xt, 0, pcc), ese.g_xt)
+            gl = Dcat[..., pin + (n - 1) * pst:]
+            for i in reversed(range(n)):
+                x = (cat, pin + (i - 1) * pst, pst) if i else (cat, 0, pin)
+                add = Dcat[..., x[1]:x[1] + x[2]]
+                if i == 0 and m.identity:  # the module input's three terms: (D_cat[x] + G_out) + layer 0's input gradient
+                    head = SumGrads(device, add, g, **common)
+                    head.src = {}
+                    layers[f"{sname}.{mname}.sum"] = head
+                    add = head.da
+                gl = conv(f"{sname}.{mname}.{i}", seq_conv(m.layers[i]), seq_norm(m.layers[i]), x, (cat, pin + i * pst, pst), gl, add=add)
+            g = gl  # the gradient at the module's input: the previous module's G_out
+        if stage.has_pool and si > 0:
+            prev = names[si - 1]
+            b, h, w_, c = acts[prev + ".out"]
+            pool = Pool3Grads(device, B, h, w_, c, bind((prev + ".out", 0, c)), g, add=G.get(prev), **common)
+            pool.src = dict(x=(prev + ".out", 0, c))
+            layers[sname + ".pool"] = pool
+            g = pool.da
+    if stem and not getattr(vov, names[0]).has_pool:
+        first = f"{names[0]}.{next(iter(getattr(vov, names[0]).named_children()))[0]}.cat"
+        (c2, n2, _), (c3, n3, _) = vov.stem_seqs[1], vov.stem_seqs[2]
+        s2, s3 = getattr(vov.stem, c2), getattr(vov.stem, c3)
+        g = conv("stem_3", s3, getattr(vov.stem, n3), ("stem.1", 0, int(s3.weight.shape[1])), (first, 0, int(s3.weight.shape[0])), g)
+        g = conv("stem_2", s2, getattr(vov.stem, n2), ("stem.0", 0, int(s2.weight.shape[1])), ("stem.1", 0, int(s2.weight.shape[0])), g)
+    return layers, g
+
+
+def vovnet_param_grads(named, layers):
+    """{parameter name: gradient of the parameter's shape} from the layers of `vovnet_backward`; `named`: {id(parameter): name}."""
+    params = {}
+    for lay in layers.values():
+        fc = getattr(lay, "fc", None)
+        if fc is not None:
+            if id(fc.weight) in named:
+                params[named[id(fc.weight)]] = lay.d_fc_w.view(fc.weight.shape).clone()
+            if id(fc.bias) in named:
+                params[named[id(fc.bias)]] = lay.d_fc_b.clone()
+            continue
+        conv = getattr(lay, "conv", None)
+        if conv is None:
+            continue
+        if id(conv.weight) in named:
+            params[named[id(conv.weight)]] = lay.dw.view(lay.Cout, lay.ksize, lay.ksize, lay.Cin).permute(0, 3, 1, 2).contiguous()
+        got = norm_param_grads(conv, lay.norm, lay.scale, lay.q, lay.r)
+        for key, p in (("norm.weight", getattr(lay.norm, "weight", None)), ("norm.bias", getattr(lay.norm, "bias", None))):
+            if key in got and id(p) in named:
+                params[named[id(p)]] = got[key]
+    return params
+
+
 def norm_param_grads(conv, norm, scale, q, r):
     """Gradients of one level's share of a tower layer's per-channel parameters from the kernels' sums q = sum g and r = sum g * conv:
     {"norm.weight", "norm.bias", "bias"} as far as the modules have them as parameters.  The forward is layers.fold_norm's:
@@ -923,7 +1180,10 @@ class LossPlan(ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
     def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
-                 fpn_grads=False, backbone_grads=False, stem_grads=False):
+                 fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False):
+        self.with_vovnet_grads = bool(vovnet_grads)  # (`vovnet_grads` itself is the read-out method)
+        if self.with_vovnet_grads:  # before anything is built or launched
+            check_vovnet_backward(model.backbone.bottom_up, model)
         self.with_stem_grads = bool(stem_grads)  # (read by the trunk: the stem keeps its intermediates and the normalised image)
         # (`backbone_grads`, `fpn_grads` and `tower_grads` themselves are the read-out methods)
         self.with_backbone_grads = bool(backbone_grads) or self.with_stem_grads
@@ -933,7 +1193,7 @@ class LossPlan(ForwardPlan):
             raise NotImplementedError(f"stem gradients need an even canvas ({Hp} x {Wp}): the stem's lowering sizes level1 as floor(H / 2), the stride-2 "
                                       "backward as ceil(H / 2); canvases padded to the FPN's size divisibility are always even")
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
-        self.with_fpn_grads = bool(fpn_grads) or self.with_backbone_grads
+        self.with_fpn_grads = bool(fpn_grads) or self.with_backbone_grads or self.with_vovnet_grads
         self.keep_tower_outputs = bool(tower_grads) or self.with_fpn_grads
         self.pred_grads = bool(pred_grads) or self.keep_tower_outputs
         self.grads = bool(grads) or self.pred_grads
@@ -1003,6 +1263,8 @@ class LossPlan(ForwardPlan):
             self._backbone_grads(model)
         if self.with_stem_grads:
             self._stem_grads(model)
+        if self.with_vovnet_grads:
+            self._vovnet_grads(model)
 
     def _loss_grads(self, a):
         """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
@@ -1283,6 +1545,68 @@ class LossPlan(ForwardPlan):
         tens = {"backbone_level0": self.stem_layers["level1.0"].da.permute(0, 3, 1, 2).clone(),
                 "backbone_base_layer": self.stem_layers["level0.0"].da.permute(0, 3, 1, 2).clone()}
         return tens, dla_param_grads(named, self.stem_layers)
+
+    def _vovnet_grads(self, model):
+        """The VoVNet-V2 backbone's backward behind the FPN's (include/dd3d_hip.h states it; `vovnet_backward` lays out the calls): stage5
+        down to stage2, then stem_3 and stem_2 -- per OSA module one eSE call (four launches), one weight-gradient and one input-gradient
+        call per convolution, one elementwise sum under `identity`, one launch per 3x3 max-pool -- on the main stream, still one hipGraph.  The chain ends at the gradient of
+        stem_1's stored output; stem_1's filter has no gradient.  Every call shares the one slab of weight-gradient partials, sized for
+        its largest user."""
+        dev, B = self.device, self.B
+        vov = model.backbone.bottom_up
+        if not self.use_planes:
+            raise NotImplementedError("vovnet_grads follows the split-plane data flow; DD3D_PLANES=0 and the f32 arithmetic have no tested backward")
+        pred_act_mode(self)  # (names the reduced modes, which have no loader)
+        views = {}
+        for name, b in self.bufs.items():
+            if name in ("stem.0", "stem.1") or (name.split(".")[0] in vov.stage_names and name.rsplit(".", 1)[-1] in ("cat", "xt", "out")):
+                views[name] = b.view()
+        acts = {k: (act_binding(self, v), v.H, v.W, v.C) for k, v in views.items()}
+        G = {}
+        for n, (d, c) in self.backbone_feature_grads.items():
+            assert c == d.shape[-1], (n, c, tuple(d.shape))
+            G[n] = d
+        if vov.stage_names[-1] not in G:
+            raise NotImplementedError(f"vovnet_grads needs the FPN to read {vov.stage_names[-1]} (FE.FPN.IN_FEATURES = {list(model.backbone.in_features)})")
+        s0 = views["stem.0"]
+        rows, qrows = vovnet_slab_words(B, vov, s0.H, s0.W)
+        part, qpart = self.tower_slab
+        # the whole slab, whoever sizes it (as _backbone_grads: the towers' prefix may pass the budget by one tower slice per level)
+        slack = 4 * len(self.features) * max(lay.Cout * 9 * lay.Cin for lay in self.tower_layers.values())
+        assert 4 * rows <= hip.TG_SLAB_BYTES and 4 * max(rows, part.numel()) <= hip.TG_SLAB_BYTES + slack, \
+            f"the backward's slab ({4 * max(rows, part.numel())} bytes) exceeds DD3D_TG_SLAB_BYTES"
+        if part.numel() < rows or qpart.numel() < qrows:  # (the towers' and the FPN's calls take a prefix of the larger slab)
+            alloc = torch.empty if self.dry_run else torch.zeros
+            part = alloc(max(rows, part.numel()), dtype=torch.float32, device=dev)
+            qpart = alloc(max(qrows, qpart.numel()), dtype=torch.float32, device=dev)
+            for lay in list(self.tower_layers.values()) + [l for l in self.fpn_layers.values() if l.with_wgrad]:
+                lay.part, lay.qpart = part, qpart
+                lay.args.part, lay.args.qpart = part.data_ptr(), qpart.data_ptr()
+            self.tower_slab = (part, qpart)
+        self.vovnet_layers, self.stem1_grad = vovnet_backward(dev, B, vov, G, acts, self._vec, slab=self.tower_slab)
+        for key, lay in self.vovnet_layers.items():
+            self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), "vovnet_grads." + key, dict(kind="vovnet_grads", layer=key)))
+        # as for the FPN: every stored tensor read above must still hold the forward's values when the backward runs
+        used = []
+        for lay in self.vovnet_layers.values():
+            for ref in lay.src.values():
+                if ref is not None and ref[0] not in used:
+                    used.append(ref[0])
+        self.vovnet_reads = [views[k].buf.name for k in used]
+        for k in used:
+            assert self.bufs.get(views[k].buf.name) is views[k].buf, f"the buffer {views[k].buf.name!r} the VoVNet backward reads was replaced"
+        if not self.dry_run:
+            addrs = [(views[k].pptr or views[k].ptr) for k in used]
+            assert len(set(addrs)) == len(addrs), "two tensors the VoVNet backward reads share storage"
+
+    def vovnet_grads(self):
+        """(the gradient at stem_1's stored output, VoVNet parameter gradients) of the last run, copies: {backbone_stem_1: (B, 64, Hp / 2,
+        Wp / 2)} -- not yet masked by that tensor's own ReLU -- and {name in model.named_parameters(): tensor of the parameter's shape} for
+        every parameter of backbone.bottom_up but stem.stem_1/*, float32."""
+        if not self.with_vovnet_grads:
+            raise RuntimeError("this LossPlan was built without vovnet_grads=True")
+        named = {id(p): k for k, p in self.model.named_parameters()}
+        return {"backbone_stem_1": self.stem1_grad.permute(0, 3, 1, 2).clone()}, vovnet_param_grads(named, self.vovnet_layers)
 
     def tower_grads(self):
         """(FPN-output gradients, tower parameter gradients) of the last run, copies: {feature<l>: (B, C, h_l, w_l)} and {name in

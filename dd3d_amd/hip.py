@@ -339,6 +339,40 @@ def backbone_grad_slices(B, H, W, Cin, Cout, ksize, stride):
     return (units + ups - 1) // ups
 
 
+VG_MAX_CIN, VG_MAX_COUT, EG_MAX_RSPLIT = 2144, 1024, 64
+
+
+class EseGradArgs(C.Structure):
+    """`dd3d_ese_grad_args`."""
+    _fields_ = [
+        ("xt", C.c_void_p), ("g", C.c_void_p), ("fc_w", C.c_void_p), ("fc_b", C.c_void_p), ("part", C.c_void_p), ("m", C.c_void_p), ("z", C.c_void_p),
+        ("s", C.c_void_p), ("dz", C.c_void_p), ("u", C.c_void_p), ("g_xt", C.c_void_p), ("d_fc_w", C.c_void_p), ("d_fc_b", C.c_void_p),
+        ("B", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("rsplit", C.c_int32), ("xt_mode", C.c_int32), ("xt_pitch", C.c_int32),
+        ("g_pitch", C.c_int32), ("gxt_pitch", C.c_int32), ("xt_plane_scale", C.c_float), ("reserved", C.c_int32)
+    ]
+
+
+class Pool3GradArgs(C.Structure):
+    """`dd3d_pool3_grad_args`."""
+    _fields_ = [
+        ("x", C.c_void_p), ("g", C.c_void_p), ("add", C.c_void_p), ("da", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("C", C.c_int32), ("x_mode", C.c_int32), ("x_pitch", C.c_int32), ("g_pitch", C.c_int32), ("add_pitch", C.c_int32), ("da_pitch", C.c_int32),
+        ("x_plane_scale", C.c_float)
+    ]
+
+
+def pool3_out(n):
+    """Output size of MaxPool2d(3, 2, ceil_mode=True) on n >= 3 rows (dd3d_maxpool3x3s2_ceil_nhwc's rule): ceil((n - 3) / 2) + 1, minus one
+    when the last window would start outside the map."""
+    o = (n - 3 + 1) // 2 + 1
+    return o - 1 if (o - 1) * 2 >= n else o
+
+
+def ese_grad_rsplit(HW):
+    """Row splits of one dd3d_ese_backward call: the forward gate's rule (a split per 256 rows, at most EG_MAX_RSPLIT)."""
+    return max(1, min(EG_MAX_RSPLIT, HW // 256))
+
+
 SG_UNIT, SG_TARGET_SLICES, SG_MIN_UNITS_PER_SLICE, SG_MAX_UNITS_PER_SLICE = 64, 512, 8, 64
 STEM_GRAD_SHAPES = ((7, 1, 4, 16), (3, 1, 16, 16), (3, 2, 16, 32))  # (ksize, stride, Cin, Cout) of base_layer, level0.0, level1.0
 
@@ -379,7 +413,9 @@ EXPORTS = [
     "dd3d_tower_wgrad", "dd3d_tower_dgrad", "dd3d_tower_grad_slices", "dd3d_tower_grad_layout",
     "dd3d_fpn_wgrad", "dd3d_fpn_dgrad", "dd3d_fpn_grad_slices", "dd3d_fpn_grad_layout",
     "dd3d_backbone_wgrad", "dd3d_backbone_dgrad", "dd3d_backbone_grad_slices", "dd3d_maxpool2x2_backward", "dd3d_backbone_grad_layout",
-    "dd3d_stem_wgrad", "dd3d_stem_dgrad", "dd3d_stem_grad_slices", "dd3d_stem_grad_layout"
+    "dd3d_stem_wgrad", "dd3d_stem_dgrad", "dd3d_stem_grad_slices", "dd3d_stem_grad_layout",
+    "dd3d_vovnet_conv_wgrad", "dd3d_vovnet_conv_dgrad", "dd3d_vovnet_conv_grad_slices", "dd3d_vovnet_add", "dd3d_ese_backward", "dd3d_maxpool3x3s2_ceil_backward",
+    "dd3d_vovnet_grad_layout"
 ]
 
 
@@ -485,6 +521,14 @@ def lib():
     L.dd3d_stem_grad_slices.argtypes = [C.POINTER(StemGradArgs)]
     L.dd3d_stem_grad_slices.restype = C.c_int64
     L.dd3d_stem_grad_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_vovnet_conv_wgrad.argtypes = [C.POINTER(BackboneGradArgs), C.c_void_p]
+    L.dd3d_vovnet_conv_dgrad.argtypes = [C.POINTER(BackboneGradArgs), C.c_void_p]
+    L.dd3d_vovnet_conv_grad_slices.argtypes = [C.POINTER(BackboneGradArgs)]
+    L.dd3d_vovnet_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p]
+    L.dd3d_vovnet_conv_grad_slices.restype = C.c_int64
+    L.dd3d_ese_backward.argtypes = [C.POINTER(EseGradArgs), C.c_void_p]
+    L.dd3d_maxpool3x3s2_ceil_backward.argtypes = [C.POINTER(Pool3GradArgs), C.c_void_p]
+    L.dd3d_vovnet_grad_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

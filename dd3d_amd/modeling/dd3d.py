@@ -119,7 +119,8 @@ class DD3D(nn.Module):
         self._evict_plans()
         return plan
 
-    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False, stem_grads=False):
+    def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False, stem_grads=False,
+                      vovnet_grads=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
         `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
         backward behind it as well (parameter and tower-output gradients; implies `grads`); `tower_grads`: the plan that goes on through
@@ -127,13 +128,15 @@ class DD3D(nn.Module):
         goes on through the FPN (its parameter gradients and the gradient at the backbone's output features; implies `tower_grads`);
         `backbone_grads`: the plan that goes on through DLA-34's level5 .. level2 (their parameter gradients and the gradient at the stem's
         output; implies `fpn_grads`); `stem_grads`: the plan that goes on through the stem (base_layer, level0, level1: their parameter
-        gradients and the gradients at base_layer's and level0's outputs; implies `backbone_grads`)."""
+        gradients and the gradients at base_layer's and level0's outputs; implies `backbone_grads`); `vovnet_grads`: the plan of a VoVNet-V2
+        model that goes on from the FPN through stage5 .. stage2, stem_3 and stem_2 (their parameter gradients and the gradient at stem_1's
+        output; implies `fpn_grads`; a DLA model raises NotImplementedError naming `stem_grads`)."""
         from dd3d_amd.engine.losses import LossPlan
         key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + \
-            (("stem_grads", ) if stem_grads else ("backbone_grads", ) if backbone_grads else ("fpn_grads", ) if fpn_grads else ("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
+            (("vovnet_grads", ) if vovnet_grads else ("stem_grads", ) if stem_grads else ("backbone_grads", ) if backbone_grads else ("fpn_grads", ) if fpn_grads else ("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
         plan = self._plans.pop(key, None)
         if plan is None:
-            plan = LossPlan(self, B, Hp, Wp, stem_grads=True) if stem_grads else LossPlan(self, B, Hp, Wp, backbone_grads=True) if backbone_grads else LossPlan(self, B, Hp, Wp, fpn_grads=True) if fpn_grads else LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
+            plan = LossPlan(self, B, Hp, Wp, vovnet_grads=True) if vovnet_grads else LossPlan(self, B, Hp, Wp, stem_grads=True) if stem_grads else LossPlan(self, B, Hp, Wp, backbone_grads=True) if backbone_grads else LossPlan(self, B, Hp, Wp, fpn_grads=True) if fpn_grads else LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
                 LossPlan(self, B, Hp, Wp, grads=True) if grads else LossPlan(self, B, Hp, Wp)
             if self.use_graph:
                 plan.capture()
@@ -297,7 +300,7 @@ class DD3D(nn.Module):
     # ------------------------------------------------------------------ training losses (gradients: head maps and the predictor layer)
     @torch.no_grad()
     def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
-                       stem_grads=False):
+                       stem_grads=False, **branch):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
@@ -325,16 +328,30 @@ class DD3D(nn.Module):
         also holds backbone_level0 and backbone_base_layer -- the gradients at level0's and base_layer's outputs, (B, 16, Hp, Wp), neither
         masked by its tensor's own ReLU yet -- and `param_grads` also backbone.bottom_up.base_layer / level0.0 / level1.0 (.weight; a BN
         backbone's .norm.weight / .norm.bias; a norm-less backbone's .bias): for DLA-34 its keys are then those of named_parameters().
+        With `vovnet_grads` (VoVNet-V2 models: V-19-eSE, V-39-eSE, V-57-eSE, V-99-eSE) the result has the form of `fpn_grads` and the
+        backward goes on through the bottom-up network, stage5 down to stage2, stem_3 and stem_2: everything `fpn_grads` returns, bit for
+        bit (backbone_stage2..5 stay the FPN's contribution at those features), `grads` also holds backbone_stem_1 -- the gradient at
+        stem_1's stored output, (B, 64, Hp / 2, Wp / 2), not yet masked by that tensor's own ReLU -- and `param_grads` also every
+        parameter of backbone.bottom_up except stem.stem_1/* (each OSA module's layers.<i>.<n>_<i>/conv.weight, concat.<n>_concat/conv.weight,
+        ese.fc.weight and ese.fc.bias; stem.stem_2/conv.weight and stem.stem_3/conv.weight; a BN backbone's norm weights and biases).
+        stem_1's filter (3x3 stride 2 on the four-channel image) has no gradient yet.  DLA models raise NotImplementedError naming
+        `stem_grads`; the slim and depthwise specs, DD3D_PLANES=0 and the reduced arithmetic modes raise too.  (`vovnet_grads` is a
+        keyword of its own, not one more level of the chain head_grads .. stem_grads above, whose named parameters
+        tests/test_loss_plan_history.py pins: it is taken from `**branch`, and any other extra keyword is a TypeError.)
         The filter copies the backward reads are snapshots taken when the plan is built; there is no optimiser, no batch-statistics
         norm and no model.train().  V2-99, the Bottleneck DLA variants, force_generic_dla and the reduced arithmetic modes raise
         NotImplementedError."""
         from dd3d_amd.engine import relax_arithmetic
+        vovnet_grads = bool(branch.pop("vovnet_grads", False))
+        if branch:
+            raise TypeError(f"compute_losses() got an unexpected keyword argument {next(iter(branch))!r}")
         gt = [x["instances"] for x in batched_inputs]
         while True:
             backbone_grads = backbone_grads or stem_grads
-            fpn_grads = fpn_grads or backbone_grads
+            fpn_grads = fpn_grads or backbone_grads or vovnet_grads
             tower_grads = tower_grads or fpn_grads
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), stem_grads=True) if stem_grads else \
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), vovnet_grads=True) if vovnet_grads else \
+                self.get_loss_plan(*self.canvas_size(batched_inputs), stem_grads=True) if stem_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), backbone_grads=True) if backbone_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), fpn_grads=True) if fpn_grads else \
                 self.get_loss_plan(*self.canvas_size(batched_inputs), tower_grads=True) if tower_grads else \
@@ -366,6 +383,9 @@ class DD3D(nn.Module):
                 if stem_grads:
                     st, sparams = plan.stem_grads()
                     towers, params = dict(towers, **st), dict(params, **sparams)
+                if vovnet_grads:
+                    vt, vparams = plan.vovnet_grads()
+                    towers, params = dict(towers, **vt), dict(params, **vparams)
                 return losses, dict(plan.head_grads(), **towers), params
             return (losses, plan.head_grads()) if head_grads else losses
 

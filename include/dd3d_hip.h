@@ -1150,6 +1150,102 @@ int dd3d_stem_dgrad(const dd3d_stem_grad_args* args, void* stream);
 int64_t dd3d_stem_grad_slices(const dd3d_stem_grad_args* args);
 int dd3d_stem_grad_layout(int64_t* out, int32_t n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the VoVNet-V2 backbone, stage5 down to stem_2 (csrc/vovnet_grads.hip; the wide convolution entry points live beside the
+ * kernels they launch in csrc/backbone_grads.hip): the specs whose channel counts are multiples of 32 (V-19-eSE, V-39-eSE, V-57-eSE,
+ * V-99-eSE; vovnet.py:188-273; BackboneLowering._vovnet).  n(.), the ReLU masks and G_t as in the DLA section.  One OSA module with input
+ * x, concat buffer cat = [x | l0 | .. | l(n-1)], pre-eSE tensor xt and output `out`:
+ *   op        forward                                       backward
+ *   eSE       out = xt * s (+ x under `identity`)           dd3d_ese_backward: G_xt, d fc_w, d fc_b (below); under identity G_out also
+ *             s = hsigmoid(fc_w . mean_hw(xt) + fc_b)       reaches x (module input row)
+ *   concat    xt = relu(n(concat1x1 . cat))                 dWc = wgrad([xt > 0] G_xt, cat), D_cat = dgrad([xt > 0] G_xt, Wc), written once
+ *                                                           over the whole concat width and read by slices
+ *   layer i   l_i = relu(n(conv3x3(l_(i-1))))  (l_(-1) = x)  g_i = [l_i > 0] G_li: dW_i = wgrad(g_i, l_(i-1)),
+ *                                                           i > 0: G_l(i-1) = D_cat[l_(i-1)] + dgrad(g_i, W_i)        (G_l(n-1) = D_cat[l_(n-1)])
+ *   input                                                   G_x = (D_cat[x] + G_out) + dgrad(g_0, W_0) under identity, else D_cat[x] + dgrad(g_0, W_0);
+ *                                                           the three terms: one elementwise launch T = D_cat[x] + G_out (dd3d_vovnet_add),
+ *                                                           then T is layer 0's `add`
+ *   max-pool  x = maxpool3x3s2_ceil(prev stage's out)       G_prev_out = F_prev_out + the gathered window gradients (dd3d_maxpool3x3s2_ceil_backward)
+ *   stem_3    cat2[x] = relu(n(conv3x3_s2(stem_2 out)))     dW = wgrad([x > 0] G_x, stem_2 out), G_stem2 = dgrad_s2([x > 0] G_x, W)
+ *   stem_2    stem_2 out = relu(n(conv3x3(stem_1 out)))     dW = wgrad([. > 0] G_stem2, stem_1 out), G_stem1 = dgrad(.) -- not masked by stem_1's
+ *                                                           own ReLU; stem_1's filter has no gradient here
+ * F_t: the FPN's gradient at a stage output.  The order of every sum is the order written here; none uses float atomics.
+ *
+ * dd3d_vovnet_conv_wgrad / dd3d_vovnet_conv_dgrad / dd3d_vovnet_conv_grad_slices: dd3d_backbone_wgrad / dd3d_backbone_dgrad /
+ *   dd3d_backbone_grad_slices -- the same arguments, kernels, sums, orders, slab rule, tile choice and rejections -- with the limits
+ *   Cin <= DD3D_VG_MAX_CIN and Cout <= DD3D_VG_MAX_COUT (multiples of 32).  The kernels themselves are untouched: a module input's third
+ *   term is summed beforehand by
+ * dd3d_vovnet_add: out[p][c] = a[p][c] + b[p][c] over npix pixels and C channels (a multiple of 4), f32 NHWC with pitches (multiples of 4,
+ *   16-byte aligned pointers); operands may be channel slices of wider buffers.  One launch, thread = (pixel, four channels); every word
+ *   of the C channels of out is written.
+ *
+ * dd3d_ese_backward: with m[b][c] = (sum_hw xt[b,hw,c]) / HW, z[b][c] = sum_ci fc_w[c][ci] * m[b][ci] + fc_b[c], s = clamp(z + 3, 0, 6) / 6:
+ *     ds[b][c] = sum_hw g[b,hw,c] * xt[b,hw,c]           dz = ds / 6 where -3 < z < 3, else an exact 0
+ *     u[b][c]  = (sum_co fc_w[co][c] * dz[b][co]) / HW    g_xt[b,hw,c] = g[b,hw,c] * s[b][c] + u[b][c]      (not masked by xt's own ReLU)
+ *     d_fc_w[co][ci] = sum_b dz[b][co] * m[b][ci]         d_fc_b[co] = sum_b dz[b][co]
+ *   m and z are recomputed from the stored xt (any DD3D_PG_ACT_* storage) in the pass that forms ds; nothing of the forward's workspace is
+ *   read.  Four launches: (1) block = (32 channels, row split rs of `rsplit`, image): the rows rs * ceil(HW / rsplit) .. of the split, eight
+ *   row lanes of every eighth row each, the lanes added in lane order -> part[b][rs][{sum xt, sum g xt}][c]; (2) block = (four channels
+ *   co, image), a wave per co: the splits in split order -> m, ds; z over ci by lanes of every 64th ci, then a butterfly over the lanes (the
+ *   forward gate's order) -> m, z, s, dz; (3) thread = (co, ci): d_fc_w over b in image order; thread = (b, c): u in chunks of 32 co, a
+ *   fresh sum per chunk, the chunks added in chunk order; thread = co: d_fc_b over b; (4) thread = (pixel, four channels): g_xt.  One
+ *   writer and a fixed order per sum: two runs agree bit for bit.  Written: every word of part's rows in use, m, z, s, dz, u ([B][C] each),
+ *   d_fc_w, d_fc_b and the C channels of g_xt; nothing beyond them.  Safe under stream capture.
+ *   Rejected (-1, the message starts with the entry point's name): C not a multiple of 32 or above DD3D_VG_MAX_COUT, rsplit outside
+ *   1 .. DD3D_EG_MAX_RSPLIT, pitches not a multiple of 4 or too small, an unknown storage, null pointers, B * HW above DD3D_BG_MAX_PIXELS.
+ *
+ * dd3d_maxpool3x3s2_ceil_backward: the backward of MaxPool2d(3, 2, ceil_mode=True) (dd3d_maxpool3x3s2_ceil_nhwc) as a gather.  Output
+ *   sizes: Ho = ceil((H - 3) / 2) + 1, minus one when the last window would start outside the map ((Ho - 1) * 2 >= H); Wo alike.  Window
+ *   (oy, ox) covers the rows 2 oy .. min(2 oy + 2, H - 1) and the columns alike (clipped at the border, no padding); its arg-max is
+ *   recomputed from the stored input x (any DD3D_PG_ACT_* storage); among equal maxima the first in row-major window order wins (torch's
+ *   max_pool2d on the CPU).  thread = (input pixel, channel): v = add[b,y,x,c] (or nothing), then for the at most 2 x 2 windows that
+ *   contain the pixel, in ascending (oy, ox): v += g[b,oy,ox,c] where the pixel is that window's arg-max.  Without `add` the sum starts
+ *   at 0: bit for bit torch's CPU backward.  One launch; every word of the C channels of da is written.  H, W >= 3.
+ *   Rejected: H or W below 3, C not a multiple of 32 or above DD3D_VG_MAX_COUT, pitches, storages, null pointers, the pixel limit.
+ * dd3d_vovnet_grad_layout: sizeof and field offsets of both structs.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_VG_MAX_CIN 2144                /* the concat 1x1 of stage5: 1024 + 5 * 224 */
+#define DD3D_VG_MAX_COUT 1024
+#define DD3D_EG_MAX_RSPLIT 64
+typedef struct dd3d_ese_grad_args {         /* host memory; every pointer is device memory */
+  const void* xt;                           /* the stored pre-eSE tensor [B][HW], storage xt_mode */
+  const float* g;                           /* gradient at the module output: [B][HW][g_pitch] */
+  const float* fc_w;                        /* [C][C] */
+  const float* fc_b;                        /* [C] */
+  float* part;                              /* scratch [B][rsplit][2][C] */
+  float* m;                                 /* [B][C] */
+  float* z;                                 /* [B][C] */
+  float* s;                                 /* [B][C] */
+  float* dz;                                /* [B][C] */
+  float* u;                                 /* [B][C] */
+  float* g_xt;                              /* [B][HW][gxt_pitch] */
+  float* d_fc_w;                            /* [C][C] */
+  float* d_fc_b;                            /* [C] */
+  int32_t B, HW, C, rsplit;
+  int32_t xt_mode, xt_pitch;                /* DD3D_PG_ACT_*; floats per pixel (DD3D_PG_ACT_F32) */
+  int32_t g_pitch, gxt_pitch;
+  float xt_plane_scale;                     /* DD3D_PG_ACT_F16X2 */
+  int32_t reserved;                         /* 0; ignored */
+} dd3d_ese_grad_args;
+typedef struct dd3d_pool3_grad_args {       /* host memory; every pointer is device memory */
+  const void* x;                            /* the pool's stored input [B][H][W], storage x_mode */
+  const float* g;                           /* gradient at the pooled tensor: [B][Ho][Wo][g_pitch] */
+  const float* add;                         /* [B][H][W][add_pitch], or NULL */
+  float* da;                                /* [B][H][W][da_pitch] */
+  int32_t B, H, W, C;
+  int32_t x_mode, x_pitch;
+  int32_t g_pitch, add_pitch, da_pitch;
+  float x_plane_scale;
+} dd3d_pool3_grad_args;
+int dd3d_vovnet_conv_wgrad(const dd3d_backbone_grad_args* args, void* stream);
+int dd3d_vovnet_conv_dgrad(const dd3d_backbone_grad_args* args, void* stream);
+int64_t dd3d_vovnet_conv_grad_slices(const dd3d_backbone_grad_args* args);
+int dd3d_vovnet_add(const float* a, const float* b, float* out, int64_t npix, int32_t C, int32_t a_pitch, int32_t b_pitch, int32_t out_pitch,
+                    void* stream);
+int dd3d_ese_backward(const dd3d_ese_grad_args* args, void* stream);
+int dd3d_maxpool3x3s2_ceil_backward(const dd3d_pool3_grad_args* args, void* stream);
+int dd3d_vovnet_grad_layout(int64_t* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
