@@ -276,26 +276,70 @@ def pred_act_mode(plan):
     raise NotImplementedError(f"predictor gradients read f32, f16x2 or bf16x3 tower outputs; the arithmetic mode {name!r} has no loader")
 
 
-class PredGroupGrads:
+class GradCall:
+    """What the gradient calls below share: the guarded allocator of their outputs, the pitch rule of the NHWC tensors they are handed,
+    the weight-gradient outputs of the convolution calls and the launch.
+
+    `ENTRIES`: (library entry, label of its error check) of the launches in their order -- the weight gradient, run when `with_wgrad`,
+    then the input gradient, run when `with_dgrad`; a call of one launch lists one entry.  `_raw` holds (tensor, numel) of every tensor
+    the call allocates and its kernels write: `numel` words of output, then `guard` words the kernels must leave at `fill`."""
+    ENTRIES = ()
+    with_wgrad = with_dgrad = True
+
+    def __init__(self, device, fill, guard):
+        self._raw, self._new = [], (device, float(fill), guard)
+
+    def out(self, *shape):
+        device, fill, guard = self._new
+        numel = int(np.prod(shape))
+        t = torch.full((numel + guard, ), fill, dtype=torch.float32, device=device)
+        self._raw.append((t, numel))
+        return t[:numel].view(*shape)
+
+    @staticmethod
+    def pitch(t):
+        """Words between two pixels of an NHWC tensor or channel slice (torch leaves the stride of a dimension of size one arbitrary:
+        a tensor one pixel wide whose stride is below its channel count has the channel count)."""
+        return int(t.stride(-2)) if t.shape[-2] > 1 or t.stride(-2) >= t.shape[-1] else int(t.shape[-1])
+
+    def wgrad_outputs(self, a, slab, Cout, KK, level=(), total=()):
+        """The weight gradient's outputs and their six addresses in `a`: the partials `part` [n_slices, Cout, KK] and `qpart`
+        [n_slices, Cout] -- the shared `slab`, or the call's own -- then `dw_level` [*level, Cout, KK], `dw` [*total, Cout, KK] and the
+        per-channel sums `q`, `r` [*level, Cout]."""
+        if slab is None:
+            slab = (self.out(self.n_slices, Cout, KK), self.out(self.n_slices, Cout))
+        self.part, self.qpart = slab
+        assert self.part.numel() >= self.n_slices * Cout * KK and self.qpart.numel() >= self.n_slices * Cout
+        self.dw_level, self.dw = self.out(*level, Cout, KK), self.out(*total, Cout, KK)
+        self.q, self.r = self.out(*level, Cout), self.out(*level, Cout)
+        a.part, a.qpart, a.dw_level, a.dw = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw))
+        a.q, a.r = self.q.data_ptr(), self.r.data_ptr()
+
+    def launch(self, lib, st):
+        for (entry, label), on in zip(self.ENTRIES, (self.with_wgrad, self.with_dgrad)):
+            if on:
+                hip.check(getattr(lib, entry)(C.byref(self.args), st), label)
+
+    def guards_intact(self, fill):
+        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
+
+
+class PredGroupGrads(GradCall):
     """Buffers and dd3d_pred_grad_args of one predictor group (the predictors fused into one head map, reading one tower).
 
     `act`: per-level device address of the tower output in the storage `act_mode` names; `g`, `maps`: per-level NHWC tensors of pitch
     `g_pitch`; `w`: per-level [n, 3, 3, Cin] filters, the SAME tensor on the levels that share a module; `bias`, `scale`: per-level [n];
     `lo`: [n] or None; `slot`: int32 [n] or None.  Outputs are allocated here, filled with `fill` and followed by `guard` words of it."""
+    ENTRIES = (("dd3d_predictor_wgrad", "predictor_wgrad"), ("dd3d_predictor_dgrad", "predictor_dgrad"))
+
     def __init__(self, device, B, level_hw, Cin, n, g_pitch, act, act_mode, act_pitch, plane_scale, g, maps, w, bias, scale, lo=None, slot=None,
                  fill=0.0, guard=0):
+        GradCall.__init__(self, device, fill, guard)
         L = len(level_hw)
         self.B, self.level_hw, self.Cin, self.n, self.L = B, list(level_hw), Cin, n, L
         self.keep = (g, maps, w, bias, scale, lo, slot)
         a = hip.PredGradArgs()
-        self._raw = []
-
-        def out(*shape):
-            numel = int(np.prod(shape))
-            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
-            self._raw.append((t, numel))
-            return t[:numel].view(*shape)
-
+        out = self.out
         K9 = 9 * Cin
         self.n_slices = hip.pred_grad_slices(B, level_hw)
         self.part, self.qpart = out(self.n_slices, n, K9), out(self.n_slices, n)
@@ -319,13 +363,6 @@ class PredGroupGrads:
         # the first level of every distinct filter: the rows of dw / db that are written
         self.owners = [l for l in range(L) if all(w[m].data_ptr() != w[l].data_ptr() for m in range(l))]
 
-    def launch(self, lib, st):
-        hip.check(lib.dd3d_predictor_wgrad(C.byref(self.args), st), "predictor_wgrad")
-        hip.check(lib.dd3d_predictor_dgrad(C.byref(self.args), st), "predictor_dgrad")
-
-    def guards_intact(self, fill):
-        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
-
 
 def act_binding(plan, view):
     """(DD3D_PG_ACT_* mode, device address, pitch, plane scale) of the storage a plan keeps `view` in: its split planes where it has
@@ -335,43 +372,30 @@ def act_binding(plan, view):
     return hip.PG_ACT_F32, view.ptr, int(view.pitch), 1.0
 
 
-class TowerLayerGrads:
+class TowerLayerGrads(GradCall):
     """Buffers and dd3d_tower_grad_args of one tower layer over all levels.
 
     `x`, `y`: per level (mode, device address, pitch, plane scale) of the layer's input and stored output (one mode per side); `g`:
     per-level NHWC gradient tensors of pitch `g_pitch`; `w`: the [Cout, 3, 3, Cin] filter; `scale`: per-level [Cout]; `da_add`: per-level
     [B, h, w, Cin] tensors or None; `slab`: (part, qpart) shared with other layers that run in stream order, or None to allocate them.
     Outputs are allocated here, filled with `fill` and followed by `guard` words of it."""
+    ENTRIES = (("dd3d_tower_wgrad", "tower_wgrad"), ("dd3d_tower_dgrad", "tower_dgrad"))
+
     def __init__(self, device, B, level_hw, Cin, Cout, x, y, g, g_pitch, w, scale, da_add=None, slab=None, fill=0.0, guard=0, dgrad_rows=0):
+        GradCall.__init__(self, device, fill, guard)
         L = len(level_hw)
         self.B, self.level_hw, self.Cin, self.Cout, self.L = B, list(level_hw), Cin, Cout, L
         self.keep = (g, w, scale, da_add, slab)
         a = hip.TowerGradArgs()
-        self._raw = []
-
-        def out(*shape):
-            numel = int(np.prod(shape))
-            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
-            self._raw.append((t, numel))
-            return t[:numel].view(*shape)
-
-        K9 = 9 * Cin
         self.n_slices = hip.tower_grad_slices(B, level_hw, Cin, Cout)
-        if slab is None:
-            slab = (out(self.n_slices, Cout, K9), out(self.n_slices, Cout))
-        self.part, self.qpart = slab
-        assert self.part.numel() >= self.n_slices * Cout * K9 and self.qpart.numel() >= self.n_slices * Cout
-        self.dw_level, self.dw = out(L, Cout, K9), out(Cout, K9)
-        self.q, self.r = out(L, Cout), out(L, Cout)
-        self.da = [out(B, h, w_, Cin) for h, w_ in level_hw]
+        self.wgrad_outputs(a, slab, Cout, 9 * Cin, level=(L, ))  # one filter for all levels: dw is their sum
+        self.da = [self.out(B, h, w_, Cin) for h, w_ in level_hw]
         for l, (h, w_) in enumerate(level_hw):
             a.x[l], a.y[l] = x[l][1] or None, y[l][1] or None
             a.g[l], a.scale[l], a.da[l] = g[l].data_ptr(), scale[l].data_ptr(), self.da[l].data_ptr()
             a.da_add[l] = da_add[l].data_ptr() if da_add is not None else None
             a.H[l], a.W[l] = int(h), int(w_)
         a.w = w.data_ptr()
-        a.part, a.qpart, a.dw_level, a.dw = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw))
-        a.q, a.r = self.q.data_ptr(), self.r.data_ptr()
         a.num_levels, a.B, a.Cin, a.Cout, a.g_pitch = L, int(B), int(Cin), int(Cout), int(g_pitch)
         a.x_mode, a.x_pitch, a.x_plane_scale = int(x[0][0]), int(x[0][2]), float(x[0][3])
         a.y_mode, a.y_pitch, a.y_plane_scale = int(y[0][0]), int(y[0][2]), float(y[0][3])
@@ -379,15 +403,8 @@ class TowerLayerGrads:
         a.n_slices, a.dgrad_rows = self.n_slices, int(dgrad_rows)
         self.args = a
 
-    def launch(self, lib, st):
-        hip.check(lib.dd3d_tower_wgrad(C.byref(self.args), st), "tower_wgrad")
-        hip.check(lib.dd3d_tower_dgrad(C.byref(self.args), st), "tower_dgrad")
 
-    def guards_intact(self, fill):
-        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
-
-
-class FpnConvGrads:
+class FpnConvGrads(GradCall):
     """Buffers and dd3d_fpn_grad_args of one FPN convolution per level (k x k, stride 1 or 2, a filter per level, no ReLU).
 
     `in_hw`: per-level INPUT sizes; `x`: per level (mode, device address, pitch, plane scale) of the convolution's input, or None for a
@@ -397,35 +414,22 @@ class FpnConvGrads:
     tensor, or "prev" for the input gradient of the level before (the transposed top-down path inside one call); `slab`: (part, qpart)
     shared with other calls that run in stream order, or None to allocate them.  Outputs are allocated here, filled with `fill` and
     followed by `guard` words of it."""
+    ENTRIES = (("dd3d_fpn_wgrad", "fpn_wgrad"), ("dd3d_fpn_dgrad", "fpn_dgrad"))
+
     def __init__(self, device, B, in_hw, Cin, Cout, ksize, stride, x, g, g_pitch, w, scale, mask=None, add=None, pool=None, in_relu=False, slab=None,
                  fill=0.0, guard=0, dgrad_rows=0, wgrad=True, dgrad=True):
+        GradCall.__init__(self, device, fill, guard)
         L = len(in_hw)
         self.B, self.in_hw, self.Cin, self.Cout, self.L, self.ksize, self.stride = B, list(in_hw), Cin, Cout, L, ksize, stride
         self.out_hw = [((h + stride - 1) // stride, (w_ + stride - 1) // stride) for h, w_ in in_hw]
         self.keep = (g, w, scale, add, pool, slab)
         self.with_wgrad, self.with_dgrad = bool(wgrad), bool(dgrad)
         a = hip.FpnGradArgs()
-        self._raw = []
-
-        def out(*shape):
-            numel = int(np.prod(shape))
-            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
-            self._raw.append((t, numel))
-            return t[:numel].view(*shape)
-
-        KK = ksize * ksize * Cin
         self.n_slices = hip.fpn_grad_slices(B, in_hw, Cin, Cout, ksize, stride)
         self.part = self.qpart = self.dw_level = self.dw = self.q = self.r = None
         if wgrad:
-            if slab is None:
-                slab = (out(self.n_slices, Cout, KK), out(self.n_slices, Cout))
-            self.part, self.qpart = slab
-            assert self.part.numel() >= self.n_slices * Cout * KK and self.qpart.numel() >= self.n_slices * Cout
-            self.dw_level, self.dw = out(L, Cout, KK), out(L, Cout, KK)
-            self.q, self.r = out(L, Cout), out(L, Cout)
-            a.part, a.qpart, a.dw_level, a.dw = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw))
-            a.q, a.r = self.q.data_ptr(), self.r.data_ptr()
-        self.da = [out(B, h, w_, Cin) for h, w_ in in_hw] if dgrad else None
+            self.wgrad_outputs(a, slab, Cout, ksize * ksize * Cin, level=(L, ), total=(L, ))  # a filter per level
+        self.da = [self.out(B, h, w_, Cin) for h, w_ in in_hw] if dgrad else None
         for l, (h, w_) in enumerate(in_hw):
             a.x[l] = (x[l][1] or None) if x is not None else None
             a.g[l], a.w[l], a.scale[l] = g[l].data_ptr(), w[l].data_ptr(), scale[l].data_ptr()
@@ -448,17 +452,8 @@ class FpnConvGrads:
         a.n_slices, a.dgrad_rows = self.n_slices, int(dgrad_rows)
         self.args = a
 
-    def launch(self, lib, st):
-        if self.with_wgrad:
-            hip.check(lib.dd3d_fpn_wgrad(C.byref(self.args), st), "fpn_wgrad")
-        if self.with_dgrad:
-            hip.check(lib.dd3d_fpn_dgrad(C.byref(self.args), st), "fpn_dgrad")
 
-    def guards_intact(self, fill):
-        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
-
-
-class BackboneConvGrads:
+class BackboneConvGrads(GradCall):
     """Buffers and dd3d_backbone_grad_args of ONE backbone convolution (k x k, stride 1 or 2; csrc/backbone_grads.hip).
 
     `H`, `W`: the INPUT's sizes; `x`, `y`: (mode, device address, pitch, plane scale) of the stored input and of the stored output whose
@@ -468,37 +463,25 @@ class BackboneConvGrads:
     it) or None; `da`: a [B, H, W, Cin] slice of a wider gradient buffer to write into, or None to allocate it; `slab`: (part, qpart)
     shared with other calls that run in stream order, or None to allocate them.  Outputs are allocated here, filled with `fill` and
     followed by `guard` words of it."""
+    ENTRIES = (("dd3d_backbone_wgrad", "backbone_wgrad"), ("dd3d_backbone_dgrad", "backbone_dgrad"))
+
     def __init__(self, device, B, H, W, Cin, Cout, ksize, stride, x, y, g, w, scale, add=None, res=None, da=None, slab=None, fill=0.0, guard=0,
                  dgrad_rows=0, dgrad_group=0, wgrad=True, dgrad=True):
+        GradCall.__init__(self, device, fill, guard)
         self.B, self.H, self.W, self.Cin, self.Cout, self.ksize, self.stride = B, int(H), int(W), Cin, Cout, ksize, stride
         self.Ho, self.Wo = (self.H + stride - 1) // stride, (self.W + stride - 1) // stride
         self.keep = (g, w, scale, add, res, slab)
         self.scale = scale
         self.with_wgrad, self.with_dgrad = bool(wgrad), bool(dgrad)
         a = hip.BackboneGradArgs()
-        self._raw = []
-
-        def out(*shape):
-            numel = int(np.prod(shape))
-            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
-            self._raw.append((t, numel))
-            return t[:numel].view(*shape)
-
-        pitch = lambda t: int(t.stride(-2)) if t.shape[-2] > 1 or t.stride(-2) >= t.shape[-1] else int(t.shape[-1])
-        KK = ksize * ksize * Cin
+        pitch = self.pitch
         assert tuple(g.shape) == (B, self.Ho, self.Wo, Cout) and g.stride(-1) == 1, (tuple(g.shape), (B, self.Ho, self.Wo, Cout))
         self.n_slices = hip.backbone_grad_slices(B, self.H, self.W, Cin, Cout, ksize, stride)
         self.part = self.qpart = self.dw_level = self.dw = self.q = self.r = None
         if wgrad:
-            if slab is None:
-                slab = (out(self.n_slices, Cout, KK), out(self.n_slices, Cout))
-            self.part, self.qpart = slab
-            assert self.part.numel() >= self.n_slices * Cout * KK and self.qpart.numel() >= self.n_slices * Cout
-            self.dw_level, self.dw, self.q, self.r = out(Cout, KK), out(Cout, KK), out(Cout), out(Cout)
-            a.part, a.qpart, a.dw_level, a.dw = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw))
-            a.q, a.r = self.q.data_ptr(), self.r.data_ptr()
+            self.wgrad_outputs(a, slab, Cout, ksize * ksize * Cin)
         if dgrad:
-            self.da = out(B, self.H, self.W, Cin) if da is None else da
+            self.da = self.out(B, self.H, self.W, Cin) if da is None else da
             assert tuple(self.da.shape) == (B, self.H, self.W, Cin) and self.da.stride(-1) == 1
             a.da, a.da_pitch = self.da.data_ptr(), pitch(self.da)
         else:
@@ -523,28 +506,19 @@ class BackboneConvGrads:
         a.n_slices, a.dgrad_rows, a.dgrad_group = self.n_slices, int(dgrad_rows), int(dgrad_group)
         self.args = a
 
-    def launch(self, lib, st):
-        if self.with_wgrad:
-            hip.check(lib.dd3d_backbone_wgrad(C.byref(self.args), st), "backbone_wgrad")
-        if self.with_dgrad:
-            hip.check(lib.dd3d_backbone_dgrad(C.byref(self.args), st), "backbone_dgrad")
 
-    def guards_intact(self, fill):
-        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
-
-
-class PoolGrads:
+class PoolGrads(GradCall):
     """Buffers and dd3d_pool_grad_args of one 2x2 max-pool backward: `x` the binding of the pool's stored input ([B, H, W, C]), `g` the
     gradient at the pooled tensor (None with `res` alone), `res`: (a second part of it, binding of the stored tensor that masks it) or
     None, `add` [B, H, W, C] or None.  `da` is allocated here (filled with `fill`, followed by `guard` words)."""
+    ENTRIES = (("dd3d_maxpool2x2_backward", "maxpool2x2_backward"), )
+
     def __init__(self, device, B, H, W, Cc, x, g, add=None, res=None, fill=0.0, guard=0):
+        GradCall.__init__(self, device, fill, guard)
         self.B, self.H, self.W, self.C = B, int(H), int(W), int(Cc)
         self.keep = (g, add, res)
-        numel = B * self.H * self.W * self.C
-        t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
-        self._raw = [(t, numel)]
-        self.da = t[:numel].view(B, self.H, self.W, self.C)
-        pitch = lambda v: int(v.stride(-2)) if v.shape[-2] > 1 or v.stride(-2) >= v.shape[-1] else int(v.shape[-1])
+        self.da = self.out(B, self.H, self.W, self.C)
+        pitch = self.pitch
         a = hip.PoolGradArgs()
         a.x, a.da, a.res_y_plane_scale = x[1] or None, self.da.data_ptr(), 1.0
         for t in ([g] if g is not None else []) + ([res[0]] if res is not None else []):
@@ -562,14 +536,8 @@ class PoolGrads:
             a.add, a.add_pitch = add.data_ptr(), pitch(add)
         self.args = a
 
-    def launch(self, lib, st):
-        hip.check(lib.dd3d_maxpool2x2_backward(C.byref(self.args), st), "maxpool2x2_backward")
 
-    def guards_intact(self, fill):
-        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
-
-
-class StemConvGrads:
+class StemConvGrads(GradCall):
     """Buffers and dd3d_stem_grad_args of ONE stem convolution (csrc/stem_grads.hip): (ksize, stride, Cin, Cout) one of
     hip.STEM_GRAD_SHAPES.
 
@@ -579,39 +547,27 @@ class StemConvGrads:
     slice of a wider gradient buffer to write into, or None to allocate it; `slab`: (part, qpart) shared with other calls that run in
     stream order, or None to allocate them; `wgrad_blocks`: blocks of the weight gradient's main launch (0: one per slice).  Outputs are
     allocated here, filled with `fill` and followed by `guard` words of it."""
+    ENTRIES = (("dd3d_stem_wgrad", "stem_wgrad"), ("dd3d_stem_dgrad", "stem_dgrad"))
+
     def __init__(self, device, B, H, W, Cin, Cout, ksize, stride, x, y, g, w, scale, da=None, slab=None, fill=0.0, guard=0, wgrad_blocks=0,
                  wgrad=True, dgrad=True):
+        GradCall.__init__(self, device, fill, guard)
         self.B, self.H, self.W, self.Cin, self.Cout, self.ksize, self.stride = B, int(H), int(W), Cin, Cout, ksize, stride
         self.Ho, self.Wo = (self.H + stride - 1) // stride, (self.W + stride - 1) // stride
         self.keep = (x, g, w, scale, slab)
         self.scale = scale
         self.with_wgrad, self.with_dgrad = bool(wgrad), bool(dgrad)
         a = hip.StemGradArgs()
-        self._raw = []
-
-        def out(*shape):
-            numel = int(np.prod(shape))
-            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
-            self._raw.append((t, numel))
-            return t[:numel].view(*shape)
-
-        pitch = lambda t: int(t.stride(-2)) if t.shape[-2] > 1 or t.stride(-2) >= t.shape[-1] else int(t.shape[-1])
-        KK = ksize * ksize * Cin
+        pitch = self.pitch
         assert tuple(g.shape) == (B, self.Ho, self.Wo, Cout) and g.stride(-1) == 1, (tuple(g.shape), (B, self.Ho, self.Wo, Cout))
         self.n_slices = hip.stem_grad_slices(B, self.H, self.W, Cin, Cout, ksize, stride)
         self.part = self.qpart = self.dw_level = self.dw = self.q = self.r = self.da = None
         if wgrad:
             assert tuple(x.shape) == (B, self.H, self.W, Cin) and x.stride(-1) == 1, (tuple(x.shape), (B, self.H, self.W, Cin))
-            if slab is None:
-                slab = (out(self.n_slices, Cout, KK), out(self.n_slices, Cout))
-            self.part, self.qpart = slab
-            assert self.part.numel() >= self.n_slices * Cout * KK and self.qpart.numel() >= self.n_slices * Cout
-            self.dw_level, self.dw, self.q, self.r = out(Cout, KK), out(Cout, KK), out(Cout), out(Cout)
-            a.part, a.qpart, a.dw_level, a.dw = (t.data_ptr() for t in (self.part, self.qpart, self.dw_level, self.dw))
-            a.q, a.r = self.q.data_ptr(), self.r.data_ptr()
+            self.wgrad_outputs(a, slab, Cout, ksize * ksize * Cin)
             a.x, a.x_pitch = x.data_ptr(), pitch(x)
         if dgrad:
-            self.da = out(B, self.H, self.W, Cin) if da is None else da
+            self.da = self.out(B, self.H, self.W, Cin) if da is None else da
             assert tuple(self.da.shape) == (B, self.H, self.W, Cin) and self.da.stride(-1) == 1
             a.da, a.da_pitch = self.da.data_ptr(), pitch(self.da)
         a.y, a.y_mode, a.y_pitch, a.y_plane_scale = y[1] or None, int(y[0]), int(y[2]), float(y[3])
@@ -620,62 +576,40 @@ class StemConvGrads:
         a.n_slices, a.wgrad_blocks = self.n_slices, int(wgrad_blocks)
         self.args = a
 
-    def launch(self, lib, st):
-        if self.with_wgrad:
-            hip.check(lib.dd3d_stem_wgrad(C.byref(self.args), st), "stem_wgrad")
-        if self.with_dgrad:
-            hip.check(lib.dd3d_stem_dgrad(C.byref(self.args), st), "stem_dgrad")
-
-    def guards_intact(self, fill):
-        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
-
 
 class VovnetConvGrads(BackboneConvGrads):
     """BackboneConvGrads through dd3d_vovnet_conv_wgrad / dd3d_vovnet_conv_dgrad: the same call and kernels under the limits
     hip.VG_MAX_CIN / hip.VG_MAX_COUT."""
-    def launch(self, lib, st):
-        if self.with_wgrad:
-            hip.check(lib.dd3d_vovnet_conv_wgrad(C.byref(self.args), st), "vovnet_conv_wgrad")
-        if self.with_dgrad:
-            hip.check(lib.dd3d_vovnet_conv_dgrad(C.byref(self.args), st), "vovnet_conv_dgrad")
+    ENTRIES = (("dd3d_vovnet_conv_wgrad", "vovnet_conv_wgrad"), ("dd3d_vovnet_conv_dgrad", "vovnet_conv_dgrad"))
 
 
-class SumGrads:
+class SumGrads(GradCall):
     """One dd3d_vovnet_add launch: `da` [B, H, W, C] = a + b, two f32 NHWC gradients of that shape (slices may be given).  `da` is
     allocated here (filled with `fill`, followed by `guard` words)."""
     def __init__(self, device, a, b, fill=0.0, guard=0):
+        GradCall.__init__(self, device, fill, guard)
         assert tuple(a.shape) == tuple(b.shape) and a.dim() == 4 and a.stride(-1) == 1 and b.stride(-1) == 1, (tuple(a.shape), tuple(b.shape))
         self.keep = (a, b)
-        numel = a.numel()
-        t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
-        self._raw = [(t, numel)]
-        self.da = t[:numel].view(*a.shape)
-        pitch = lambda v: int(v.stride(-2)) if v.shape[-2] > 1 or v.stride(-2) >= v.shape[-1] else int(v.shape[-1])
-        self.call = (a.data_ptr(), b.data_ptr(), self.da.data_ptr(), int(numel // a.shape[-1]), int(a.shape[-1]), pitch(a), pitch(b), int(a.shape[-1]))
+        self.da = self.out(*a.shape)
+        self.call = (a.data_ptr(), b.data_ptr(), self.da.data_ptr(), int(a.numel() // a.shape[-1]), int(a.shape[-1]), self.pitch(a), self.pitch(b),
+                     int(a.shape[-1]))
 
-    def launch(self, lib, st):
+    def launch(self, lib, st):  # (positional arguments: there is no args struct to pass by reference)
         hip.check(lib.dd3d_vovnet_add(*self.call, st), "vovnet_add")
 
-    def guards_intact(self, fill):
-        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
 
-
-class EseGrads:
+class EseGrads(GradCall):
     """Buffers and dd3d_ese_grad_args of one eSE gate's backward (csrc/vovnet_grads.hip): `xt` the binding of the stored pre-eSE tensor
     ([B, H, W, C]), `g` the gradient at the module output ([B, H, W, C], a slice may be given), `fc_w` [C, C] and `fc_b` [C] on the
     device.  Outputs are allocated here, filled with `fill` and followed by `guard` words of it: g_xt [B, H, W, C] (not masked by xt's own
     ReLU), d_fc_w [C, C], d_fc_b [C], and the per-image vectors m, z, s, dz, u [B, C]."""
+    ENTRIES = (("dd3d_ese_backward", "ese_backward"), )
+
     def __init__(self, device, B, H, W, Cc, xt, g, fc_w, fc_b, rsplit=None, fill=0.0, guard=0):
+        GradCall.__init__(self, device, fill, guard)
         self.B, self.H, self.W, self.C = B, int(H), int(W), int(Cc)
         self.keep = (g, fc_w, fc_b)
-        self._raw = []
-
-        def out(*shape):
-            numel = int(np.prod(shape))
-            t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
-            self._raw.append((t, numel))
-            return t[:numel].view(*shape)
-
+        out = self.out
         HW = self.H * self.W
         self.rsplit = hip.ese_grad_rsplit(HW) if rsplit is None else int(rsplit)
         assert tuple(g.shape) == (B, self.H, self.W, self.C) and g.stride(-1) == 1, (tuple(g.shape), (B, self.H, self.W, self.C))
@@ -686,33 +620,27 @@ class EseGrads:
         self.da = self.g_xt
         a = hip.EseGradArgs()
         a.xt, a.xt_mode, a.xt_pitch, a.xt_plane_scale = xt[1] or None, int(xt[0]), int(xt[2]), float(xt[3])
-        a.g, a.g_pitch = g.data_ptr(), int(g.stride(-2)) if g.shape[-2] > 1 or g.stride(-2) >= g.shape[-1] else int(g.shape[-1])
+        a.g, a.g_pitch = g.data_ptr(), self.pitch(g)
         a.fc_w, a.fc_b = fc_w.data_ptr(), fc_b.data_ptr()
         a.part, a.m, a.z, a.s, a.dz, a.u = (t.data_ptr() for t in (self.part, self.m, self.z, self.s, self.dz, self.u))
         a.g_xt, a.gxt_pitch, a.d_fc_w, a.d_fc_b = self.g_xt.data_ptr(), self.C, self.d_fc_w.data_ptr(), self.d_fc_b.data_ptr()
         a.B, a.HW, a.C, a.rsplit = int(B), HW, self.C, self.rsplit
         self.args = a
 
-    def launch(self, lib, st):
-        hip.check(lib.dd3d_ese_backward(C.byref(self.args), st), "ese_backward")
 
-    def guards_intact(self, fill):
-        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
-
-
-class Pool3Grads:
+class Pool3Grads(GradCall):
     """Buffers and dd3d_pool3_grad_args of one MaxPool2d(3, 2, ceil_mode=True) backward: `x` the binding of the pool's stored input
     ([B, H, W, C]), `g` the gradient at the pooled tensor ([B, pool3_out(H), pool3_out(W), C], a slice may be given), `add` [B, H, W, C] or
     None.  `da` is allocated here (filled with `fill`, followed by `guard` words)."""
+    ENTRIES = (("dd3d_maxpool3x3s2_ceil_backward", "maxpool3x3s2_ceil_backward"), )
+
     def __init__(self, device, B, H, W, Cc, x, g, add=None, fill=0.0, guard=0):
+        GradCall.__init__(self, device, fill, guard)
         self.B, self.H, self.W, self.C = B, int(H), int(W), int(Cc)
         self.Ho, self.Wo = hip.pool3_out(self.H), hip.pool3_out(self.W)
         self.keep = (g, add)
-        numel = B * self.H * self.W * self.C
-        t = torch.full((numel + guard, ), float(fill), dtype=torch.float32, device=device)
-        self._raw = [(t, numel)]
-        self.da = t[:numel].view(B, self.H, self.W, self.C)
-        pitch = lambda v: int(v.stride(-2)) if v.shape[-2] > 1 or v.stride(-2) >= v.shape[-1] else int(v.shape[-1])
+        self.da = self.out(B, self.H, self.W, self.C)
+        pitch = self.pitch
         assert tuple(g.shape) == (B, self.Ho, self.Wo, self.C) and g.stride(-1) == 1, (tuple(g.shape), (B, self.Ho, self.Wo, self.C))
         a = hip.Pool3GradArgs()
         a.x, a.g, a.g_pitch, a.da, a.da_pitch = x[1] or None, g.data_ptr(), pitch(g), self.da.data_ptr(), self.C
@@ -722,12 +650,6 @@ class Pool3Grads:
             assert tuple(add.shape) == (B, self.H, self.W, self.C) and add.stride(-1) == 1
             a.add, a.add_pitch = add.data_ptr(), pitch(add)
         self.args = a
-
-    def launch(self, lib, st):
-        hip.check(lib.dd3d_maxpool3x3s2_ceil_backward(C.byref(self.args), st), "maxpool3x3s2_ceil_backward")
-
-    def guards_intact(self, fill):
-        return all(bool((t[n:] == fill).all()) for t, n in self._raw)
 
 
 def slice_binding(bind, c0, npix):
@@ -740,6 +662,15 @@ def slice_binding(bind, c0, npix):
         return (mode, addr + 4 * c0, pitch, scale)
     assert c0 % 32 == 0, c0
     return (mode, addr + (c0 // 32) * npix * (128 if mode == hip.PG_ACT_F16X2 else 192), pitch, scale)
+
+
+def filter_copy(conv, device, cin=None):
+    """The [Cout, k, k, Cin] float32 copy of a convolution's filter the gradient kernels read, on `device`; with `cin` the input channels
+    are padded with zero filters up to that width (a buffer's pad channels, the image's fourth channel)."""
+    w = conv.weight.detach().float()
+    if cin is not None and w.shape[1] < cin:
+        w = torch.cat([w, torch.zeros(w.shape[0], cin - w.shape[1], *w.shape[2:], dtype=w.dtype, device=w.device)], 1)
+    return w.permute(0, 2, 3, 1).contiguous().to(device)
 
 
 def check_dla_backward(dla, model=None):
@@ -803,10 +734,9 @@ def dla_backward(device, B, dla, G, acts, vec, slab=None, fill=0.0, guard=0):
         k, cin, cout = int(mod.weight.shape[-1]), int(mod.weight.shape[1]), int(mod.weight.shape[0])
         assert x[2] == cin and (y is None or y[2] == cout), (key, x, y)
         H, W = acts[x[0]][1], acts[x[0]][2]
-        w = mod.weight.detach().float().permute(0, 2, 3, 1).contiguous().to(device)
-        lay = BackboneConvGrads(device, B, H, W, cin, cout, k, stride, bind(x), bind(y) if y is not None else None, g, w, vec(fold_norm(mod, None)[0]),
-                                add=add, res=(res[0], bind(res[1])) if res is not None else None, slab=slab, **common)
-        lay.conv, lay.src = mod, dict(x=x, y=y, res_y=res[1] if res is not None else None)
+        lay = BackboneConvGrads(device, B, H, W, cin, cout, k, stride, bind(x), bind(y) if y is not None else None, g, filter_copy(mod, device),
+                                vec(fold_norm(mod, None)[0]), add=add, res=(res[0], bind(res[1])) if res is not None else None, slab=slab, **common)
+        lay.conv, lay.norm, lay.src = mod, getattr(mod, "norm", None), dict(x=x, y=y, res_y=res[1] if res is not None else None)
         layers[key] = lay
         return lay.da
 
@@ -869,21 +799,27 @@ def dla_backward(device, B, dla, G, acts, vec, slab=None, fill=0.0, guard=0):
     return layers, g
 
 
+def conv_param_grads(named, lay, conv, norm, dw, scale, q, r):
+    """{parameter name: gradient of the parameter's shape} of ONE convolution and its norm from the outputs of the call `lay` that ran its
+    backward: the filter's from `dw` (lay.Cout x k x k x lay.Cin words; the gradients of the buffer's pad channels are dropped), the
+    per-channel parameters' from `scale`, `q` and `r` (norm_param_grads); `named`: {id(parameter): name}."""
+    params = {}
+    k, cin = lay.ksize, int(conv.weight.shape[1])
+    if id(conv.weight) in named:
+        params[named[id(conv.weight)]] = dw.view(lay.Cout, k, k, lay.Cin)[..., :cin].permute(0, 3, 1, 2).contiguous()
+    got = norm_param_grads(conv, norm, scale, q, r)
+    for key, p in (("norm.weight", getattr(norm, "weight", None)), ("norm.bias", getattr(norm, "bias", None)), ("bias", conv.bias)):
+        if key in got and id(p) in named:
+            params[named[id(p)]] = got[key]
+    return params
+
+
 def dla_param_grads(named, layers, prefix=""):
     """{parameter name: gradient of the parameter's shape} from the layers of `dla_backward`; `named`: {id(parameter): name}."""
     params = {}
     for lay in layers.values():
-        conv = getattr(lay, "conv", None)
-        if conv is None:
-            continue
-        k, cin = lay.ksize, int(conv.weight.shape[1])
-        if id(conv.weight) in named:
-            params[named[id(conv.weight)]] = lay.dw.view(lay.Cout, k, k, lay.Cin)[..., :cin].permute(0, 3, 1, 2).contiguous()
-        norm = getattr(conv, "norm", None)
-        got = norm_param_grads(conv, norm, lay.scale, lay.q, lay.r)
-        for key, p in (("norm.weight", getattr(norm, "weight", None)), ("norm.bias", getattr(norm, "bias", None)), ("bias", conv.bias)):
-            if key in got and id(p) in named:
-                params[named[id(p)]] = got[key]
+        if getattr(lay, "conv", None) is not None:
+            params.update(conv_param_grads(named, lay, lay.conv, lay.norm, lay.dw, lay.scale, lay.q, lay.r))
     return params
 
 
@@ -970,9 +906,8 @@ def vovnet_backward(device, B, vov, G, acts, vec, slab=None, fill=0.0, guard=0, 
         k, cin, cout, stride = int(mod.weight.shape[-1]), int(mod.weight.shape[1]), int(mod.weight.shape[0]), int(mod.stride)
         assert x[2] == cin and y[2] == cout, (key, x, y)
         H, W = acts[x[0]][1], acts[x[0]][2]
-        w = mod.weight.detach().float().permute(0, 2, 3, 1).contiguous().to(device)
-        lay = VovnetConvGrads(device, B, H, W, cin, cout, k, stride, bind(x), bind(y), g, w, vec(fold_norm(mod, norm)[0]), add=add, slab=slab,
-                              **common)
+        lay = VovnetConvGrads(device, B, H, W, cin, cout, k, stride, bind(x), bind(y), g, filter_copy(mod, device), vec(fold_norm(mod, norm)[0]),
+                              add=add, slab=slab, **common)
         lay.conv, lay.norm, lay.src = mod, norm, dict(x=x, y=y)
         layers[key] = lay
         return lay.da
@@ -1031,15 +966,10 @@ def vovnet_param_grads(named, layers):
             if id(fc.bias) in named:
                 params[named[id(fc.bias)]] = lay.d_fc_b.clone()
             continue
-        conv = getattr(lay, "conv", None)
-        if conv is None:
-            continue
-        if id(conv.weight) in named:
-            params[named[id(conv.weight)]] = lay.dw.view(lay.Cout, lay.ksize, lay.ksize, lay.Cin).permute(0, 3, 1, 2).contiguous()
-        got = norm_param_grads(conv, lay.norm, lay.scale, lay.q, lay.r)
-        for key, p in (("norm.weight", getattr(lay.norm, "weight", None)), ("norm.bias", getattr(lay.norm, "bias", None))):
-            if key in got and id(p) in named:
-                params[named[id(p)]] = got[key]
+        # (nothing to drop: conv() asserts lay.Cin is the filter's own width; and no "bias" entry can occur: modeling/vovnet.py builds
+        # every convolution with bias=False)
+        if getattr(lay, "conv", None) is not None:
+            params.update(conv_param_grads(named, lay, lay.conv, lay.norm, lay.dw, lay.scale, lay.q, lay.r))
     return params
 
 
@@ -1091,12 +1021,7 @@ def fpn_backward(device, B, fpn, G, acts, vec, slab=None, fill=0.0, guard=0):
     Cf = acts[f"t{stages[0]}"][3]
     layers, common = OrderedDict(), dict(slab=slab, fill=fill, guard=guard)
 
-    def filt(conv, cin):  # [Cout, k, k, cin]: the input channels padded with zero filters up to the buffer's width
-        w = conv.weight.detach().float()
-        if w.shape[1] < cin:
-            w = torch.cat([w, torch.zeros(w.shape[0], cin - w.shape[1], *w.shape[2:], dtype=w.dtype, device=w.device)], 1)
-        return w.permute(0, 2, 3, 1).contiguous().to(device)
-
+    filt = lambda conv, cin: filter_copy(conv, device, cin)  # the input channels padded with zero filters up to the buffer's width
     scale_of = lambda conv: vec(fold_norm(conv, None)[0])
     hw = lambda k: (acts[k][1], acts[k][2])
     s5 = stages[-1]
@@ -1141,14 +1066,7 @@ def fpn_param_grads(named, layers):
     for lay in layers.values():
         convs = lay.conv if isinstance(lay.conv, list) else [lay.conv]
         for l, conv in enumerate(convs):
-            k, cin = lay.ksize, int(conv.weight.shape[1])
-            if id(conv.weight) in named:
-                params[named[id(conv.weight)]] = lay.dw[l].view(lay.Cout, k, k, lay.Cin)[..., :cin].permute(0, 3, 1, 2).contiguous()
-            norm = getattr(conv, "norm", None)
-            got = norm_param_grads(conv, norm, lay.keep[2][l], lay.q[l], lay.r[l])
-            for key, p in (("norm.weight", getattr(norm, "weight", None)), ("norm.bias", getattr(norm, "bias", None)), ("bias", conv.bias)):
-                if key in got and id(p) in named:
-                    params[named[id(p)]] = got[key]
+            params.update(conv_param_grads(named, lay, conv, getattr(conv, "norm", None), lay.dw[l], lay.keep[2][l], lay.q[l], lay.r[l]))
     return params
 
 
@@ -1326,7 +1244,7 @@ class LossPlan(ForwardPlan):
         {name in model.named_parameters(): tensor of the parameter's shape}, float32."""
         if not self.pred_grads:
             raise RuntimeError("this LossPlan was built without pred_grads=True")
-        names = {id(p): k for k, p in self.model.named_parameters()}
+        names = self._named()
         towers, params = {}, {}
         for grp in self.pred_groups.values():
             for l in range(grp.L):
@@ -1379,9 +1297,8 @@ class LossPlan(ForwardPlan):
                 info = self.tower_info[(tname, i)]
                 conv = info["conv"]
                 Cout, Cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
-                w = conv.weight.detach().float().permute(0, 2, 3, 1).contiguous().to(dev)
                 lay = TowerLayerGrads(dev, self.B, level_hw, Cin, Cout, [act_binding(self, v) for v in info["x"]],
-                                      [act_binding(self, v) for v in info["y"]], g, g_pitch, w, info["scales"],
+                                      [act_binding(self, v) for v in info["y"]], g, g_pitch, filter_copy(conv, dev), info["scales"],
                                       da_add=feature_da if i == 0 else None, slab=self.tower_slab)
                 lay.conv, lay.norms, lay.tower, lay.index = conv, info["norms"], tname, i
                 self.tower_layers[(tname, i)] = lay
@@ -1390,6 +1307,64 @@ class LossPlan(ForwardPlan):
                 g, g_pitch = lay.da, Cin
             feature_da = g
         self.feature_grads = feature_da
+
+    def _grow_slab(self, rows, qrows, budget=True):
+        """Make the plan's slab of weight-gradient partials hold `rows` / `qrows` words for the stage about to be built, and re-point
+        every layer built so far that has partials at the larger one (their calls take a prefix of it).  `budget`: assert the whole
+        slab, whoever sizes it, against DD3D_TG_SLAB_BYTES."""
+        dev = self.device
+        part, qpart = self.tower_slab
+        if budget:
+            # a call's slices stay within DD3D_TG_SLAB_BYTES; the towers' rule rounds up once per pyramid level
+            # (dd3d_tower_grad_slices: "+ at most one row per level"), so their prefix may pass it by that many tower slices
+            slack = 4 * len(self.features) * max(lay.Cout * 9 * lay.Cin for lay in self.tower_layers.values())
+            assert 4 * rows <= hip.TG_SLAB_BYTES and 4 * max(rows, part.numel()) <= hip.TG_SLAB_BYTES + slack, \
+                f"the backward's slab ({4 * max(rows, part.numel())} bytes) exceeds DD3D_TG_SLAB_BYTES"
+        if part.numel() < rows or qpart.numel() < qrows:
+            alloc = torch.empty if self.dry_run else torch.zeros
+            part = alloc(max(rows, part.numel()), dtype=torch.float32, device=dev)
+            qpart = alloc(max(qrows, qpart.numel()), dtype=torch.float32, device=dev)
+            for lay in list(self.tower_layers.values()) + [l for l in getattr(self, "fpn_layers", {}).values() if l.with_wgrad]:
+                lay.part, lay.qpart = part, qpart
+                lay.args.part, lay.args.qpart = part.data_ptr(), qpart.data_ptr()
+            self.tower_slab = (part, qpart)
+
+    def _append_calls(self, kind, layers):
+        """One CallOp per layer of a backward stage, in the layers' order, on the main stream."""
+        for key, lay in layers.items():
+            self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), f"{kind}.{key}", dict(kind=kind, layer=key)))
+
+    def _check_reads(self, what, views, layers=None):
+        """Every stored tensor a backward stage reads must still hold the forward's values when the backward runs.  PlanBase.buf gives
+        every NAMED buffer a storage of its own for the life of the plan (there is no recycling allocator), so a tensor is intact as long
+        as its name still maps to the buffer the view was taken from and no two of them share storage.  `views`: the views read; with
+        `layers`, {key: view}, of which the stage reads what its layers' `src` name, in the order of first use.  Returns the buffers'
+        names."""
+        if layers is not None:
+            used = []
+            for lay in layers.values():
+                for ref in lay.src.values():
+                    if ref is not None and ref[0] not in used:
+                        used.append(ref[0])
+            views = [views[k] for k in used]
+        for v in views:
+            assert self.bufs.get(v.buf.name) is v.buf, f"the buffer {v.buf.name!r} the {what} backward reads was replaced"
+        if not self.dry_run:
+            addrs = [(v.pptr or v.ptr) for v in views]
+            assert len(set(addrs)) == len(addrs) and all(addrs), f"two tensors the {what} backward reads share storage"
+        return [v.buf.name for v in views]
+
+    def _feature_grad_inputs(self):
+        """{backbone feature name: the gradient the FPN sends it}, for a bottom-up network whose features have no pad channels."""
+        G = {}
+        for n, (d, c) in self.backbone_feature_grads.items():
+            assert c == d.shape[-1], (n, c, tuple(d.shape))
+            G[n] = d
+        return G
+
+    def _named(self):
+        """{id(parameter): its name in model.named_parameters()}: the read-outs file every gradient under its parameter's name."""
+        return {id(p): k for k, p in self.model.named_parameters()}
 
     def _fpn_grads(self, model):
         """The FPN's backward behind the towers' (include/dd3d_hip.h states it; `fpn_backward` lays out the calls): the top block (P7,
@@ -1410,28 +1385,10 @@ class LossPlan(ForwardPlan):
             v = view(name)
             G[name] = self.feature_grads[selected.index(name)] if name in selected else torch.zeros((B, v.H, v.W, Cf), dtype=torch.float32, device=dev)
             assert tuple(G[name].shape) == (B, v.H, v.W, Cf)
-        rows, qrows = fpn_slab_words(B, fpn, acts)
-        part, qpart = self.tower_slab
-        if part.numel() < rows or qpart.numel() < qrows:  # (the towers' calls take a prefix of the larger slab)
-            alloc = torch.empty if self.dry_run else torch.zeros
-            part = alloc(max(rows, part.numel()), dtype=torch.float32, device=dev)
-            qpart = alloc(max(qrows, qpart.numel()), dtype=torch.float32, device=dev)
-            for lay in self.tower_layers.values():
-                lay.part, lay.qpart = part, qpart
-                lay.args.part, lay.args.qpart = part.data_ptr(), qpart.data_ptr()
-            self.tower_slab = (part, qpart)
+        self._grow_slab(*fpn_slab_words(B, fpn, acts), budget=False)
         self.fpn_layers, self.backbone_feature_grads = fpn_backward(dev, B, fpn, G, acts, self._vec, slab=self.tower_slab)
-        for key, lay in self.fpn_layers.items():
-            self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), "fpn_grads." + key, dict(kind="fpn_grads", layer=key)))
-        # Every tensor read above must still hold the forward's values when the backward runs.  PlanBase.buf gives every NAMED buffer a
-        # storage of its own for the life of the plan (there is no recycling allocator), so a tensor is intact as long as its name still
-        # maps to the buffer the view was taken from and no two of them share storage; nothing needs pinning beyond that.
-        self.fpn_reads, self.fpn_pinned = [v.buf.name for _, v in reads], []
-        for _, v in reads:
-            assert self.bufs.get(v.buf.name) is v.buf, f"the buffer {v.buf.name!r} the FPN backward reads was replaced"
-        if not self.dry_run:
-            addrs = [(v.pptr or v.ptr) for _, v in reads]
-            assert len(set(addrs)) == len(addrs), "two tensors the FPN backward reads share storage"
+        self._append_calls("fpn_grads", self.fpn_layers)
+        self.fpn_reads, self.fpn_pinned = self._check_reads("FPN", [v for _, v in reads]), []  # (nothing needs pinning beyond the check)
 
     def fpn_grads(self):
         """(backbone-feature gradients, FPN parameter gradients) of the last run, copies: {backbone_<name>: (B, C_name, h, w)} and {name in
@@ -1439,7 +1396,7 @@ class LossPlan(ForwardPlan):
         if not self.with_fpn_grads:
             raise RuntimeError("this LossPlan was built without fpn_grads=True")
         feats = {f"backbone_{n}": d[..., :c].permute(0, 3, 1, 2).clone() for n, (d, c) in self.backbone_feature_grads.items()}
-        return feats, fpn_param_grads({id(p): k for k, p in self.model.named_parameters()}, self.fpn_layers)
+        return feats, fpn_param_grads(self._named(), self.fpn_layers)
 
     def _backbone_grads(self, model):
         """The DLA-34 backbone's backward behind the FPN's (include/dd3d_hip.h states it; `dla_backward` lays out the calls): level5 down
@@ -1454,40 +1411,11 @@ class LossPlan(ForwardPlan):
             if name.split(".")[0] in ("level2", "level3", "level4", "level5") and name.rsplit(".", 1)[-1] in ("cat", "mid", "bottom", "out"):
                 views[name] = b.view()
         acts = {k: (act_binding(self, v), v.H, v.W, v.C) for k, v in views.items()}
-        G = {}
-        for n, (d, c) in self.backbone_feature_grads.items():
-            assert c == d.shape[-1], (n, c, tuple(d.shape))
-            G[n] = d
-        rows, qrows = dla_slab_words(B, dla, l1.H, l1.W)
-        part, qpart = self.tower_slab
-        # the whole slab, whoever sizes it: a call's slices stay within DD3D_TG_SLAB_BYTES; the towers' rule rounds up once per pyramid
-        # level (dd3d_tower_grad_slices: "+ at most one row per level"), so their prefix may pass it by that many tower slices
-        slack = 4 * len(self.features) * max(lay.Cout * 9 * lay.Cin for lay in self.tower_layers.values())
-        assert 4 * rows <= hip.TG_SLAB_BYTES and 4 * max(rows, part.numel()) <= hip.TG_SLAB_BYTES + slack, \
-            f"the backward's slab ({4 * max(rows, part.numel())} bytes) exceeds DD3D_TG_SLAB_BYTES"
-        if part.numel() < rows or qpart.numel() < qrows:  # (the towers' and the FPN's calls take a prefix of the larger slab)
-            alloc = torch.empty if self.dry_run else torch.zeros
-            part = alloc(max(rows, part.numel()), dtype=torch.float32, device=dev)
-            qpart = alloc(max(qrows, qpart.numel()), dtype=torch.float32, device=dev)
-            for lay in list(self.tower_layers.values()) + [l for l in self.fpn_layers.values() if l.with_wgrad]:
-                lay.part, lay.qpart = part, qpart
-                lay.args.part, lay.args.qpart = part.data_ptr(), qpart.data_ptr()
-            self.tower_slab = (part, qpart)
+        G = self._feature_grad_inputs()
+        self._grow_slab(*dla_slab_words(B, dla, l1.H, l1.W))
         self.backbone_layers, self.level1_grad = dla_backward(dev, B, dla, G, acts, self._vec, slab=self.tower_slab)
-        for key, lay in self.backbone_layers.items():
-            self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), "backbone_grads." + key, dict(kind="backbone_grads", layer=key)))
-        # as for the FPN: every stored tensor read above must still hold the forward's values when the backward runs
-        used = []
-        for lay in self.backbone_layers.values():
-            for ref in lay.src.values():
-                if ref is not None and ref[0] not in used:
-                    used.append(ref[0])
-        self.backbone_reads = [views[k].buf.name for k in used]
-        for k in used:
-            assert self.bufs.get(views[k].buf.name) is views[k].buf, f"the buffer {views[k].buf.name!r} the backbone backward reads was replaced"
-        if not self.dry_run:
-            addrs = [(views[k].pptr or views[k].ptr) for k in used]
-            assert len(set(addrs)) == len(addrs), "two tensors the backbone backward reads share storage"
+        self._append_calls("backbone_grads", self.backbone_layers)
+        self.backbone_reads = self._check_reads("backbone", views, self.backbone_layers)
 
     def backbone_grads(self):
         """(the gradient at the stem's stored output, backbone parameter gradients) of the last run, copies: {backbone_level1: (B, C1,
@@ -1495,8 +1423,7 @@ class LossPlan(ForwardPlan):
         shape} for every parameter of backbone.bottom_up.level2 .. level5, float32."""
         if not self.with_backbone_grads:
             raise RuntimeError("this LossPlan was built without backbone_grads=True")
-        named = {id(p): k for k, p in self.model.named_parameters()}
-        return {"backbone_level1": self.level1_grad.permute(0, 3, 1, 2).clone()}, dla_param_grads(named, self.backbone_layers)
+        return {"backbone_level1": self.level1_grad.permute(0, 3, 1, 2).clone()}, dla_param_grads(self._named(), self.backbone_layers)
 
     def _stem_grads(self, model):
         """The stem's backward behind the backbone's (csrc/stem_grads.hip; include/dd3d_hip.h states it): level1.0 and level0.0 (weight
@@ -1516,24 +1443,17 @@ class LossPlan(ForwardPlan):
             xb, yv = self.bufs[xname], self.bufs[yname].view()
             cout, cin, k = int(conv.weight.shape[0]), int(xb.pitch), int(conv.weight.shape[-1])
             assert (k, int(conv.stride), cin, cout) in hip.STEM_GRAD_SHAPES and xb.has_f32 and xb.t is not None, (key, k, conv.stride, cin, cout)
-            w = torch.zeros((cout, k, k, cin), dtype=torch.float32)
-            w[..., :conv.weight.shape[1]] = conv.weight.detach().float().permute(0, 2, 3, 1)  # (the image's fourth channel: a zero filter)
+            w = filter_copy(conv, dev, cin)  # (the image's fourth channel: a zero filter)
             n = hip.stem_grad_slices(B, xb.H, xb.W, cin, cout, k, int(conv.stride))
             assert n * cout * k * k * cin <= part.numel() and n * cout <= qpart.numel(), \
                 f"stem_grads.{key}: {n} slices of {cout} x {k * k * cin} words do not fit the plan's slab of {part.numel()} words"
-            lay = StemConvGrads(dev, B, xb.H, xb.W, cin, cout, k, int(conv.stride), xb.t, act_binding(self, yv), g, w.to(dev), self._vec(fold_norm(conv, None)[0]),
+            lay = StemConvGrads(dev, B, xb.H, xb.W, cin, cout, k, int(conv.stride), xb.t, act_binding(self, yv), g, w, self._vec(fold_norm(conv, None)[0]),
                                 slab=self.tower_slab, dgrad=key != "base_layer")
-            lay.conv, lay.src = conv, dict(x=(xname, 0, cin), y=(yname, 0, cout))
+            lay.conv, lay.norm, lay.src = conv, getattr(conv, "norm", None), dict(x=(xname, 0, cin), y=(yname, 0, cout))
             self.stem_layers[key] = lay
-            self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), "stem_grads." + key, dict(kind="stem_grads", layer=key)))
             g = lay.da
-        # as for the backbone: every stored tensor read above must still hold the forward's values when the backward runs
-        self.stem_reads = ["img4", "base", "level0.0", "level1.0"]
-        for name in self.stem_reads:
-            assert name in self.bufs, f"the buffer {name!r} the stem backward reads does not exist"
-        if not self.dry_run:
-            addrs = [(v.pptr or v.ptr) for v in (self.bufs[n].view() for n in self.stem_reads)]
-            assert len(set(addrs)) == len(addrs) and all(addrs), "two tensors the stem backward reads share storage"
+        self._append_calls("stem_grads", self.stem_layers)
+        self.stem_reads = self._check_reads("stem", [self.bufs[n].view() for n in ("img4", "base", "level0.0", "level1.0")])
 
     def stem_grads(self):
         """(the gradients at level0's and base_layer's outputs, the stem's parameter gradients) of the last run, copies:
@@ -1541,10 +1461,9 @@ class LossPlan(ForwardPlan):
         model.named_parameters(): tensor of the parameter's shape} for backbone.bottom_up.base_layer / level0.0 / level1.0, float32."""
         if not self.with_stem_grads:
             raise RuntimeError("this LossPlan was built without stem_grads=True")
-        named = {id(p): k for k, p in self.model.named_parameters()}
         tens = {"backbone_level0": self.stem_layers["level1.0"].da.permute(0, 3, 1, 2).clone(),
                 "backbone_base_layer": self.stem_layers["level0.0"].da.permute(0, 3, 1, 2).clone()}
-        return tens, dla_param_grads(named, self.stem_layers)
+        return tens, dla_param_grads(self._named(), self.stem_layers)
 
     def _vovnet_grads(self, model):
         """The VoVNet-V2 backbone's backward behind the FPN's (include/dd3d_hip.h states it; `vovnet_backward` lays out the calls): stage5
@@ -1562,42 +1481,14 @@ class LossPlan(ForwardPlan):
             if name in ("stem.0", "stem.1") or (name.split(".")[0] in vov.stage_names and name.rsplit(".", 1)[-1] in ("cat", "xt", "out")):
                 views[name] = b.view()
         acts = {k: (act_binding(self, v), v.H, v.W, v.C) for k, v in views.items()}
-        G = {}
-        for n, (d, c) in self.backbone_feature_grads.items():
-            assert c == d.shape[-1], (n, c, tuple(d.shape))
-            G[n] = d
+        G = self._feature_grad_inputs()
         if vov.stage_names[-1] not in G:
             raise NotImplementedError(f"vovnet_grads needs the FPN to read {vov.stage_names[-1]} (FE.FPN.IN_FEATURES = {list(model.backbone.in_features)})")
         s0 = views["stem.0"]
-        rows, qrows = vovnet_slab_words(B, vov, s0.H, s0.W)
-        part, qpart = self.tower_slab
-        # the whole slab, whoever sizes it (as _backbone_grads: the towers' prefix may pass the budget by one tower slice per level)
-        slack = 4 * len(self.features) * max(lay.Cout * 9 * lay.Cin for lay in self.tower_layers.values())
-        assert 4 * rows <= hip.TG_SLAB_BYTES and 4 * max(rows, part.numel()) <= hip.TG_SLAB_BYTES + slack, \
-            f"the backward's slab ({4 * max(rows, part.numel())} bytes) exceeds DD3D_TG_SLAB_BYTES"
-        if part.numel() < rows or qpart.numel() < qrows:  # (the towers' and the FPN's calls take a prefix of the larger slab)
-            alloc = torch.empty if self.dry_run else torch.zeros
-            part = alloc(max(rows, part.numel()), dtype=torch.float32, device=dev)
-            qpart = alloc(max(qrows, qpart.numel()), dtype=torch.float32, device=dev)
-            for lay in list(self.tower_layers.values()) + [l for l in self.fpn_layers.values() if l.with_wgrad]:
-                lay.part, lay.qpart = part, qpart
-                lay.args.part, lay.args.qpart = part.data_ptr(), qpart.data_ptr()
-            self.tower_slab = (part, qpart)
+        self._grow_slab(*vovnet_slab_words(B, vov, s0.H, s0.W))
         self.vovnet_layers, self.stem1_grad = vovnet_backward(dev, B, vov, G, acts, self._vec, slab=self.tower_slab)
-        for key, lay in self.vovnet_layers.items():
-            self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), "vovnet_grads." + key, dict(kind="vovnet_grads", layer=key)))
-        # as for the FPN: every stored tensor read above must still hold the forward's values when the backward runs
-        used = []
-        for lay in self.vovnet_layers.values():
-            for ref in lay.src.values():
-                if ref is not None and ref[0] not in used:
-                    used.append(ref[0])
-        self.vovnet_reads = [views[k].buf.name for k in used]
-        for k in used:
-            assert self.bufs.get(views[k].buf.name) is views[k].buf, f"the buffer {views[k].buf.name!r} the VoVNet backward reads was replaced"
-        if not self.dry_run:
-            addrs = [(views[k].pptr or views[k].ptr) for k in used]
-            assert len(set(addrs)) == len(addrs), "two tensors the VoVNet backward reads share storage"
+        self._append_calls("vovnet_grads", self.vovnet_layers)
+        self.vovnet_reads = self._check_reads("VoVNet", views, self.vovnet_layers)
 
     def vovnet_grads(self):
         """(the gradient at stem_1's stored output, VoVNet parameter gradients) of the last run, copies: {backbone_stem_1: (B, 64, Hp / 2,
@@ -1605,8 +1496,7 @@ class LossPlan(ForwardPlan):
         every parameter of backbone.bottom_up but stem.stem_1/*, float32."""
         if not self.with_vovnet_grads:
             raise RuntimeError("this LossPlan was built without vovnet_grads=True")
-        named = {id(p): k for k, p in self.model.named_parameters()}
-        return {"backbone_stem_1": self.stem1_grad.permute(0, 3, 1, 2).clone()}, vovnet_param_grads(named, self.vovnet_layers)
+        return {"backbone_stem_1": self.stem1_grad.permute(0, 3, 1, 2).clone()}, vovnet_param_grads(self._named(), self.vovnet_layers)
 
     def tower_grads(self):
         """(FPN-output gradients, tower parameter gradients) of the last run, copies: {feature<l>: (B, C, h_l, w_l)} and {name in

@@ -26,6 +26,12 @@ def _as_f32_array(t):
     return np.asarray(t, dtype=np.float32)
 
 
+def _deepest(**flags):
+    """{name: True} of the first flag set -- the caller lists the loss plan's levels deepest first, each implying the ones after it --
+    or {} when none is: one plan, and one cache key, per deepest requested level of the backward."""
+    return next(({name: True} for name, on in flags.items() if on), {})
+
+
 def build_feature_extractor(cfg, input_shape=None):
     """tridet/modeling/feature_extractor/__init__.py:13-26."""
     if input_shape is None:
@@ -132,12 +138,12 @@ class DD3D(nn.Module):
         model that goes on from the FPN through stage5 .. stage2, stem_3 and stem_2 (their parameter gradients and the gradient at stem_1's
         output; implies `fpn_grads`; a DLA model raises NotImplementedError naming `stem_grads`)."""
         from dd3d_amd.engine.losses import LossPlan
-        key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + \
-            (("vovnet_grads", ) if vovnet_grads else ("stem_grads", ) if stem_grads else ("backbone_grads", ) if backbone_grads else ("fpn_grads", ) if fpn_grads else ("tower_grads", ) if tower_grads else ("pred_grads", ) if pred_grads else ("grads", ) if grads else ())
+        level = _deepest(vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads, fpn_grads=fpn_grads, tower_grads=tower_grads,
+                         pred_grads=pred_grads, grads=grads)
+        key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + tuple(level)
         plan = self._plans.pop(key, None)
         if plan is None:
-            plan = LossPlan(self, B, Hp, Wp, vovnet_grads=True) if vovnet_grads else LossPlan(self, B, Hp, Wp, stem_grads=True) if stem_grads else LossPlan(self, B, Hp, Wp, backbone_grads=True) if backbone_grads else LossPlan(self, B, Hp, Wp, fpn_grads=True) if fpn_grads else LossPlan(self, B, Hp, Wp, tower_grads=True) if tower_grads else LossPlan(self, B, Hp, Wp, pred_grads=True) if pred_grads else \
-                LossPlan(self, B, Hp, Wp, grads=True) if grads else LossPlan(self, B, Hp, Wp)
+            plan = LossPlan(self, B, Hp, Wp, **level)
             if self.use_graph:
                 plan.capture()
         self._plans[key] = plan
@@ -350,14 +356,9 @@ class DD3D(nn.Module):
             backbone_grads = backbone_grads or stem_grads
             fpn_grads = fpn_grads or backbone_grads or vovnet_grads
             tower_grads = tower_grads or fpn_grads
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), vovnet_grads=True) if vovnet_grads else \
-                self.get_loss_plan(*self.canvas_size(batched_inputs), stem_grads=True) if stem_grads else \
-                self.get_loss_plan(*self.canvas_size(batched_inputs), backbone_grads=True) if backbone_grads else \
-                self.get_loss_plan(*self.canvas_size(batched_inputs), fpn_grads=True) if fpn_grads else \
-                self.get_loss_plan(*self.canvas_size(batched_inputs), tower_grads=True) if tower_grads else \
-                self.get_loss_plan(*self.canvas_size(batched_inputs), pred_grads=True) if predictor_grads else \
-                self.get_loss_plan(*self.canvas_size(batched_inputs), grads=True) if head_grads else \
-                self.get_loss_plan(*self.canvas_size(batched_inputs))
+            level = _deepest(vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads, fpn_grads=fpn_grads,
+                             tower_grads=tower_grads, pred_grads=predictor_grads, grads=head_grads)
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), **level)
             plan.stage_gt(gt)
             self.stage_inputs(batched_inputs, plan=plan)  # (its flush ships the GT too)
             plan.run()
@@ -371,21 +372,11 @@ class DD3D(nn.Module):
             losses = plan.loss_dict(int(rb.counts[0]))
             if predictor_grads or tower_grads:
                 towers, params = plan.predictor_grads()
-                if tower_grads:
-                    feats, tparams = plan.tower_grads()
-                    towers, params = dict(towers, **feats), dict(params, **tparams)
-                if fpn_grads:
-                    bfeats, fparams = plan.fpn_grads()
-                    towers, params = dict(towers, **bfeats), dict(params, **fparams)
-                if backbone_grads:
-                    l1, bparams = plan.backbone_grads()
-                    towers, params = dict(towers, **l1), dict(params, **bparams)
-                if stem_grads:
-                    st, sparams = plan.stem_grads()
-                    towers, params = dict(towers, **st), dict(params, **sparams)
-                if vovnet_grads:
-                    vt, vparams = plan.vovnet_grads()
-                    towers, params = dict(towers, **vt), dict(params, **vparams)
+                for on, read in ((tower_grads, plan.tower_grads), (fpn_grads, plan.fpn_grads), (backbone_grads, plan.backbone_grads),
+                                 (stem_grads, plan.stem_grads), (vovnet_grads, plan.vovnet_grads)):
+                    if on:
+                        tens, more = read()
+                        towers, params = dict(towers, **tens), dict(params, **more)
                 return losses, dict(plan.head_grads(), **towers), params
             return (losses, plan.head_grads()) if head_grads else losses
 
