@@ -132,7 +132,46 @@ class ForwardPlan(PlanBase, BackboneLowering):
         return t[..., :3].permute(0, 3, 1, 2)
 
     # ------------------------------------------------------------------ heads (fcos2d.py:130-156, fcos3d.py:160-188)
-    def _heads(self, model, feats, keep_tower_outputs=False):
+    def _bn_tower_layer(self, i, bn_segs, Cf):
+        """The three ops of a tower depth's batch-statistics segments behind their raw convolution (LossPlan(batch_stats=True)):
+        `bn_segs`: (tower name, tower index, level, conv, norm, input view, raw view, output view).  Returns {(tower name, level): the
+        segment's index}, the dd3d_tower_bn_args and the statistics tensor [segments, BN_STAT_ROWS, Cf]."""
+        dev = self.device
+        a = hip.TowerBnArgs()
+        n = len(bn_segs)
+        assert n <= hip.BN_MAX_SEGS, f"{n} batch-statistics (tower, level) pairs in one layer exceed {hip.BN_MAX_SEGS}"
+        stats = torch.zeros((n, hip.BN_STAT_ROWS, Cf), dtype=torch.float32, device=dev)
+        pixels = [v.B * v.H * v.W for *_, v in bn_segs]
+        rows = hip.bn_slices(pixels)
+        if getattr(self, "bn_part", None) is None or self.bn_part.numel() < rows * 2 * Cf:  # one scratch for every layer: they run in stream order
+            self.bn_part = torch.zeros(rows * 2 * Cf, dtype=torch.float32, device=dev)
+            for other in self.tower_bn_args:
+                other.part, other.n_slices = self.bn_part.data_ptr(), self.bn_part.numel() // (2 * Cf)
+        keep, index = [stats], {}
+        planes = bool(bn_segs[0][-1].np) and self.use_planes
+        for s, (tname, t, l, conv, norm, vin, raw, out) in enumerate(bn_segs):
+            vecs = [self._vec(v) for v in (norm.weight, norm.bias, norm.running_mean, norm.running_var)]
+            keep += vecs
+            a.c[s], a.stats[s], a.N[s] = raw.ptr, stats[s].data_ptr(), pixels[s]
+            a.gamma[s], a.beta[s], a.run_mean[s], a.run_var[s] = (v.data_ptr() for v in vecs)
+            a.y[s] = (out.pptr if planes else out.ptr) or None
+            index[(tname, l)] = s
+            assert float(norm.eps) == float(bn_segs[0][4].eps)
+        a.part, a.n_slices, a.status = self.bn_part.data_ptr(), self.bn_part.numel() // (2 * Cf), self.status.data_ptr()
+        a.num_segs, a.C, a.c_pitch = n, Cf, bn_segs[0][6].pitch
+        a.math_mode, a.y_pitch = (self.math if planes else hip.MATH_F32), bn_segs[0][-1].pitch
+        a.eps, a.momentum, a.plane_scale = float(bn_segs[0][4].eps), hip.BN_MOMENTUM, float(bn_segs[0][-1].buf.plane_scale)
+        self.tower_bn_args.append(a)
+        desc = dict(segs=[dict(tower=tname, level=l, raw=raw, out=out, norm=norm) for tname, _, l, _, norm, _, raw, out in bn_segs], stats=stats)
+        op = CallOp(lambda lib, st, a=a: hip.check(lib.dd3d_bn_batch_stats(C.byref(a), st), f"bn_batch_stats {i}"), f"towers.{i}.bn_stats",
+                    dict(desc, kind="bn_batch_stats"))
+        op.keep = keep
+        self.ops.append(op)
+        self.ops.append(CallOp(lambda lib, st, a=a: hip.check(lib.dd3d_bn_apply_relu_split(C.byref(a), st), f"bn_apply_relu_split {i}"),
+                               f"towers.{i}.bn_apply", dict(desc, kind="bn_apply_relu_split", planes=planes)))
+        return index, a, stats
+
+    def _heads(self, model, feats, keep_tower_outputs=False, batch_stats=False):
         dev = self.device
         h2, h3 = model.fcos2d_head, (None if model.only_box2d else model.fcos3d_head)
         L = len(feats)
@@ -149,26 +188,57 @@ class ForwardPlan(PlanBase, BackboneLowering):
         cur = [[feats[l] for _ in range(nt)] for l in range(L)]  # current input view per (level, tower)
         # (tower name, layer) -> what the tower backward (engine.losses) needs: module, per-level norms, device scale vectors, input / output views
         self.tower_info = {} if keep_all else None
+        # Batch statistics (LossPlan(batch_stats=True)): a tower whose norm is a trainable BatchNorm2d normalises every layer with the
+        # batch's mean and variance, per level (csrc/tower_bn.hip).  Its segments leave the fused launch: a raw convolution (f32 only, no
+        # norm, no ReLU), the statistics, then the apply that writes the layer's split planes.  A plan that keeps the tower outputs keeps
+        # every layer's raw buffer too (the backward needs c where the ReLU clipped y); any other plan reuses one per level.
+        from dd3d_amd.layers import BatchNorm2d
+        level_norm = lambda conv, l: conv.norm[l] if isinstance(conv.norm, torch.nn.ModuleList) else conv.norm  # ModuleListDial (normalization.py:30-40)
+        is_bn = lambda conv: bool(batch_stats) and all(isinstance(level_norm(conv, l), BatchNorm2d) for l in range(L))
+        self.tower_bn, self.tower_bn_args, self.bn_part = OrderedDict(), [], None
+        n_bn = max([sum(1 for _, tw in towers if i < len(tw) and is_bn(tw[i])) for i in range(depth)], default=0)
+        raw_shared = None
         for i in range(depth):
             dstbufs = tbuf(f"towerL{i}") if keep_all else ping if i % 2 == 0 else pong
-            segs, meta = [], None
+            segs, meta, raw_segs, bn_segs = [], None, [], []
+            if n_bn and (keep_all or raw_shared is None):
+                raw_shared = [self.buf(f"towerraw{i}.{l}" if keep_all else f"towerraw.{l}", f.B, f.H, f.W, n_bn * Cf) for l, f in enumerate(feats)]
+            j = 0
             for t, (tname, tower) in enumerate(towers):
                 if i >= len(tower):
                     continue
                 conv = tower[i]
                 w, meta = self.pack(conv.weight)
-                info = dict(conv=conv, index=t, norms=[], scales=[], x=[], y=[])
+                bn = is_bn(conv)
+                info = dict(conv=conv, index=t, norms=[], scales=[], x=[], y=[], raw=[] if bn else None)
                 if keep_all:
                     self.tower_info[(tname, i)] = info
                 for l in range(L):
-                    # ModuleListDial: level l uses norm[l] (normalization.py:30-40)
-                    norm = conv.norm[l] if isinstance(conv.norm, torch.nn.ModuleList) else conv.norm
-                    scale, shift = fold_norm(conv, norm)
+                    norm = level_norm(conv, l)
                     out = dstbufs[l].view(t * Cf, Cf)
-                    segs.append({"in": cur[l][t], "out": out, "w": w, "scale": self._vec(scale), "bias": self._vec(shift)})
-                    info["norms"].append(norm), info["scales"].append(segs[-1]["scale"]), info["x"].append(cur[l][t]), info["y"].append(out)
+                    if bn:  # epilogue: scale ones, the conv bias or zeros; under F16X2 `descaled` divides the power-of-two scales out
+                        raw = raw_shared[l].view(j * Cf, Cf)
+                        scale = torch.ones(Cf)
+                        shift = conv.bias.detach().float().cpu() if conv.bias is not None else torch.zeros(Cf)
+                        raw_segs.append({"in": cur[l][t], "out": raw, "w": w, "scale": self._vec(scale), "bias": self._vec(shift)})
+                        bn_segs.append((tname, t, l, conv, norm, cur[l][t], raw, out))
+                        info["raw"].append(raw), info["scales"].append(raw_segs[-1]["scale"])
+                    else:
+                        scale, shift = fold_norm(conv, norm)
+                        segs.append({"in": cur[l][t], "out": out, "w": w, "scale": self._vec(scale), "bias": self._vec(shift)})
+                        info["scales"].append(segs[-1]["scale"])
+                    info["norms"].append(norm), info["x"].append(cur[l][t]), info["y"].append(out)
                     cur[l][t] = out
-            self.ops.append(ConvOp(self, meta, 1, 1, segs, relu=True, name=f"towers.{i}"))
+                j += int(bn)
+            if segs:
+                self.ops.append(ConvOp(self, meta, 1, 1, segs, relu=True, name=f"towers.{i}"))
+            if bn_segs:
+                self.ops.append(ConvOp(self, meta, 1, 1, raw_segs, relu=False, name=f"towers.{i}.raw"))
+                index, args, stats = self._bn_tower_layer(i, bn_segs, Cf)
+                for tname in dict.fromkeys(sg[0] for sg in bn_segs):
+                    conv = next(sg[3] for sg in bn_segs if sg[0] == tname)
+                    self.tower_bn[(tname, i)] = dict(conv=conv, norms=[level_norm(conv, l) for l in range(L)], stats=stats, args=args,
+                                                     segs=[index[(tname, l)] for l in range(L)])
         self.tower_out = cur
 
         C_ = model.num_classes

@@ -5,7 +5,8 @@ their parameters and the FPN outputs (csrc/tower_grads.hip), and one stage furth
 output features (csrc/fpn_grads.hip), and one stage further again through the DLA-34 backbone's level5 .. level2 to their parameters
 and the stem's output (csrc/backbone_grads.hip), and last through the stem -- base_layer, level0, level1 -- to its parameters
 (csrc/stem_grads.hip); for the VoVNet-V2 backbones, behind the FPN through stage5 .. stage2, stem_3 and stem_2 (csrc/vovnet_grads.hip and
-the wide entry points of csrc/backbone_grads.hip).  There is no optimiser, batch-statistics norm or model.train().
+the wide entry points of csrc/backbone_grads.hip).  With batch_stats=True the head towers whose norm is a trainable
+BatchNorm2d use the batch's statistics, forward and backward (csrc/tower_bn.hip).  There is no optimiser or model.train().
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -652,6 +653,49 @@ class Pool3Grads(GradCall):
         self.args = a
 
 
+class TowerBnGrads(GradCall):
+    """Buffers and dd3d_tower_bn_args of one batch-statistics tower layer's norm backward over all levels (csrc/tower_bn.hip): the
+    segments are the levels.  `raw`: per-level [B, h, w, C] f32 views' (address, pitch) of the stored convolution output; `y`: per level
+    (mode, device address, pitch, plane scale) of the stored layer output; `g`: per-level NHWC gradient tensors at y, pitch `g_pitch`;
+    `stats`: per-level [BN_STAT_ROWS, C] tensors the forward wrote; `part`: the scratch rows shared with the forward's statistics.
+    Outputs are allocated here, filled with `fill` and followed by `guard` words of it: qp [L, 2, C] (q, p) and gc, per level [B, h, w, C]."""
+    ENTRIES = (("dd3d_bn_backward_reduce", "bn_backward_reduce"), ("dd3d_bn_backward_apply", "bn_backward_apply"))
+
+    def __init__(self, device, B, level_hw, Cc, raw, y, g, g_pitch, stats, part, fill=0.0, guard=0):
+        GradCall.__init__(self, device, fill, guard)
+        L = len(level_hw)
+        self.B, self.level_hw, self.C, self.L = B, list(level_hw), Cc, L
+        self.keep = (g, stats, part)
+        self.qp = self.out(L, 2, Cc)
+        self.gc = [self.out(B, h, w_, Cc) for h, w_ in level_hw]
+        a = hip.TowerBnArgs()
+        for l, (h, w_) in enumerate(level_hw):
+            a.c[l], a.y[l], a.g[l], a.stats[l] = raw[l][0] or None, y[l][1] or None, g[l].data_ptr(), stats[l].data_ptr()
+            a.qp[l], a.gc[l], a.N[l] = self.qp[l].data_ptr(), self.gc[l].data_ptr(), int(B * h * w_)
+        assert all(v[0] == y[0][0] and v[2:] == y[0][2:] for v in y) and all(r[1] == raw[0][1] for r in raw)
+        a.num_segs, a.C, a.c_pitch, a.g_pitch = L, int(Cc), int(raw[0][1]), int(g_pitch)
+        a.y_mode, a.y_pitch, a.plane_scale = int(y[0][0]), int(y[0][2]), float(y[0][3])
+        self.n_slices = hip.bn_slices([B * h * w_ for h, w_ in level_hw])
+        assert part.numel() >= self.n_slices * 2 * Cc
+        a.part, a.n_slices = part.data_ptr(), int(part.numel() // (2 * Cc))
+        self.args = a
+
+
+def check_batch_stats(model, B, Hp, Wp):
+    """What LossPlan(batch_stats=True) refuses before anything is built: a level with one value per channel (the reference raises there
+    too, in torch's words) and trunk norms that would need batch statistics as well."""
+    import math
+    cfg = model.cfg
+    for key, node in (("FE.BACKBONE.NORM", cfg.FE.BACKBONE), ("FE.FPN.NORM", cfg.FE.FPN)):
+        if str(node.NORM) == "BN":
+            raise NotImplementedError(f"batch_stats covers the head towers; {key} = 'BN' would need batch statistics in the trunk as well")
+    for s in model.backbone_output_shape:
+        h, w = math.ceil(Hp / s.stride), math.ceil(Wp / s.stride)
+        if B * h * w < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size [{B}, {s.channels}, {h}, {w}] "
+                             f"(stride {s.stride} on a {Hp} x {Wp} canvas)")
+
+
 def slice_binding(bind, c0, npix):
     """The binding (mode, address, pitch, plane scale) of the channel slice that starts at channel `c0` of a stored buffer with `npix`
     pixels: f32 moves the pointer by channels, split planes by whole 32-channel chunk images (f16x2: 128, bf16x3: 192 bytes a pixel)."""
@@ -1086,6 +1130,12 @@ def assemble_tower_grads(model, layers, feature_grads):
         add(conv.weight, lay.dw.view(lay.Cout, 3, 3, lay.Cin).permute(0, 3, 1, 2).contiguous())
         for l in range(lay.L):
             norm = lay.norms[l]
+            bn = getattr(lay, "bn", None)
+            if bn is not None:  # batch statistics: d gamma = p, d beta = q of the norm's backward; the GEMM call's own q / r are by-products
+                add(norm.weight, bn.qp[l, 1].clone()), add(norm.bias, bn.qp[l, 0].clone())
+                if conv.bias is not None:
+                    add(conv.bias, lay.q[l].clone())  # (the sum of G_c: zero up to rounding, the norm removes the mean)
+                continue
             got = norm_param_grads(conv, norm, lay.keep[2][l], lay.q[l], lay.r[l])
             if "norm.weight" in got:
                 add(norm.weight, got["norm.weight"]), add(norm.bias, got["norm.bias"])
@@ -1098,7 +1148,10 @@ class LossPlan(ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
     def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
-                 fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False):
+                 fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False, batch_stats=False):
+        self.batch_stats = bool(batch_stats)
+        if self.batch_stats:  # before anything is built or launched
+            check_batch_stats(model, B, Hp, Wp)
         self.with_vovnet_grads = bool(vovnet_grads)  # (`vovnet_grads` itself is the read-out method)
         if self.with_vovnet_grads:  # before anything is built or launched
             check_vovnet_backward(model.backbone.bottom_up, model)
@@ -1121,7 +1174,11 @@ class LossPlan(ForwardPlan):
         self.exchange, self.camera_sharded, self.has_bev_inputs = False, False, False
         self.adopt_weight_store(model)
         self._trunk(model, B, Hp, Wp)
-        self._heads(model, self.features, keep_tower_outputs=self.keep_tower_outputs)
+        if self.batch_stats:
+            small = [(f.H, f.W) for f in self.features if f.B * f.H * f.W < 2]
+            if small:  # (check_batch_stats predicted the level sizes; these are the plan's own)
+                raise ValueError(f"Expected more than 1 value per channel when training, got a {small[0][0]} x {small[0][1]} level with a batch of {B}")
+        self._heads(model, self.features, keep_tower_outputs=self.keep_tower_outputs, batch_stats=self.batch_stats)
         self._losses(model, max_gt)
 
     def _losses(self, model, max_gt):
@@ -1291,16 +1348,34 @@ class LossPlan(ForwardPlan):
         self.tower_slab = (alloc(n_slices * words, dtype=torch.float32, device=dev), alloc(n_slices * cmax, dtype=torch.float32, device=dev))
         self.tower_layers = {}
         feature_da = None
+        # Batch-statistics layers: the norm's backward (dd3d_bn_backward_reduce / _apply) turns the gradient at y into the dense
+        # gradient G_c at the raw convolution output; the two GEMMs then run on g := G_c with scale ones and, as the stored output
+        # whose sign masks g, a plan-owned f32 tensor of ones per level (shared by all layers): the mask passes everything.
+        self.tower_ones = None
+        if self.tower_bn:
+            cmax = max(int(v["conv"].weight.shape[0]) for v in self.tower_bn.values())
+            self.tower_ones = [torch.ones((self.B, h, w_, cmax), dtype=torch.float32, device=dev) for h, w_ in level_hw]
+            raws = [v for (tname, i), info in self.tower_info.items() if info["raw"] is not None for v in info["raw"]]
+            self.tower_bn_reads = self._check_reads("tower norm", list({id(v.buf): v.buf.view() for v in raws}.values()))
         for tname in towers:
             g, g_pitch = group_of[tname].da, group_of[tname].Cin
             for i in reversed(range(depth[tname])):
                 info = self.tower_info[(tname, i)]
                 conv = info["conv"]
                 Cout, Cin = int(conv.weight.shape[0]), int(conv.weight.shape[1])
+                y_bind, bn = [act_binding(self, v) for v in info["y"]], None
+                if info["raw"] is not None:
+                    rec = self.tower_bn[(tname, i)]
+                    bn = TowerBnGrads(dev, self.B, level_hw, Cout, [(v.ptr, v.pitch) for v in info["raw"]], y_bind, g, g_pitch,
+                                      [rec["stats"][s] for s in rec["segs"]], self.bn_part)
+                    self.ops.append(CallOp(lambda lib, st, bn=bn: bn.launch(lib, st), f"tower_bn_grads.{tname}.{i}",
+                                           dict(kind="tower_bn_grads", tower=tname, layer=i)))
+                    g, g_pitch = bn.gc, Cout
+                    y_bind = [(hip.PG_ACT_F32, t.data_ptr(), int(t.shape[-1]), 1.0) for t in self.tower_ones]
                 lay = TowerLayerGrads(dev, self.B, level_hw, Cin, Cout, [act_binding(self, v) for v in info["x"]],
-                                      [act_binding(self, v) for v in info["y"]], g, g_pitch, filter_copy(conv, dev), info["scales"],
+                                      y_bind, g, g_pitch, filter_copy(conv, dev), info["scales"],
                                       da_add=feature_da if i == 0 else None, slab=self.tower_slab)
-                lay.conv, lay.norms, lay.tower, lay.index = conv, info["norms"], tname, i
+                lay.conv, lay.norms, lay.tower, lay.index, lay.bn = conv, info["norms"], tname, i, bn
                 self.tower_layers[(tname, i)] = lay
                 self.ops.append(CallOp(lambda lib, st, lay=lay: lay.launch(lib, st), f"tower_grads.{tname}.{i}",
                                        dict(kind="tower_grads", tower=tname, layer=i)))
@@ -1505,6 +1580,24 @@ class LossPlan(ForwardPlan):
         if not self.keep_tower_outputs:
             raise RuntimeError("this LossPlan was built without tower_grads=True")
         return assemble_tower_grads(self.model, self.tower_layers, self.feature_grads)
+
+    def tower_batch_stats(self):
+        """The batch statistics of the last run, copies keyed by the state-dict names of the towers' norms: under
+        `<tower>.<i>.norm.<l>.running_mean` / `.running_var` the values the reference's train() step leaves in those buffers
+        ((1 - 0.1) * running + 0.1 * batch, the variance unbiased by N / (N - 1)), under `.batch_mean` / `.batch_var` the batch's mean
+        and biased variance.  The model's own buffers are never written."""
+        if not self.batch_stats:
+            raise RuntimeError("this LossPlan was built without batch_stats=True")
+        names = {id(b): k for k, b in self.model.named_buffers()}
+        out = {}
+        for rec in self.tower_bn.values():
+            for l, norm in enumerate(rec["norms"]):
+                st = rec["stats"][rec["segs"][l]]
+                mean_name, var_name = names[id(norm.running_mean)], names[id(norm.running_var)]
+                out[mean_name], out[var_name] = st[hip.BN_ROW_RUN_MEAN].clone(), st[hip.BN_ROW_RUN_VAR].clone()
+                stem = mean_name[:-len("running_mean")]
+                out[stem + "batch_mean"], out[stem + "batch_var"] = st[hip.BN_ROW_MU].clone(), st[hip.BN_ROW_VAR].clone()
+        return out
 
     def head_grads(self):
         """The gradients of the last run as NCHW per-level tensors (copies) under the keys of the reference's head maps."""

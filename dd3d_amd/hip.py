@@ -401,6 +401,28 @@ def stem_grad_slices(B, H, W, Cin, Cout, ksize, stride):
     return (units + ups - 1) // ups
 
 
+BN_MAX_SEGS, BN_MAX_C, BN_SLICE, BN_STAT_ROWS = 24, 256, 64, 7
+BN_ROW_MU, BN_ROW_VAR, BN_ROW_S, BN_ROW_T, BN_ROW_RSTD, BN_ROW_RUN_MEAN, BN_ROW_RUN_VAR = range(7)
+BN_MOMENTUM = 0.1  # nn.BatchNorm2d's default, which the reference's get_norm("BN") uses
+
+
+class TowerBnArgs(C.Structure):
+    """`dd3d_tower_bn_args`."""
+    _fields_ = [
+        ("c", C.c_void_p * BN_MAX_SEGS), ("gamma", C.c_void_p * BN_MAX_SEGS), ("beta", C.c_void_p * BN_MAX_SEGS), ("run_mean", C.c_void_p * BN_MAX_SEGS),
+        ("run_var", C.c_void_p * BN_MAX_SEGS), ("stats", C.c_void_p * BN_MAX_SEGS), ("y", C.c_void_p * BN_MAX_SEGS), ("g", C.c_void_p * BN_MAX_SEGS),
+        ("qp", C.c_void_p * BN_MAX_SEGS), ("gc", C.c_void_p * BN_MAX_SEGS), ("part", C.c_void_p), ("status", C.c_void_p), ("N", C.c_int32 * BN_MAX_SEGS),
+        ("num_segs", C.c_int32), ("C", C.c_int32), ("c_pitch", C.c_int32), ("g_pitch", C.c_int32), ("math_mode", C.c_int32), ("y_mode", C.c_int32),
+        ("y_pitch", C.c_int32), ("n_slices", C.c_int32), ("eps", C.c_float), ("momentum", C.c_float), ("plane_scale", C.c_float), ("reserved", C.c_int32)
+    ]
+
+
+def bn_slices(pixels):
+    """Rows of `part` one dd3d_bn_batch_stats / dd3d_bn_backward_reduce call needs for segments of `pixels` pixels each (the rule of
+    dd3d_bn_slices, for plans built without a device)."""
+    return sum((n + BN_SLICE - 1) // BN_SLICE for n in pixels)
+
+
 EXPORTS = [
     "dd3d_abi_version", "dd3d_last_error", "dd3d_arch", "dd3d_build_flags", "dd3d_conv_tile_shape", "dd3d_conv_row_rings", "dd3d_conv2d_igemm_f32",
     "dd3d_preprocess_u8_nhwc4", "dd3d_maxpool2x2_nhwc", "dd3d_maxpool3x3s2_ceil_nhwc", "dd3d_ese_nhwc", "dd3d_upsample2x_add_nhwc", "dd3d_fcos_select_decode",
@@ -415,7 +437,8 @@ EXPORTS = [
     "dd3d_backbone_wgrad", "dd3d_backbone_dgrad", "dd3d_backbone_grad_slices", "dd3d_maxpool2x2_backward", "dd3d_backbone_grad_layout",
     "dd3d_stem_wgrad", "dd3d_stem_dgrad", "dd3d_stem_grad_slices", "dd3d_stem_grad_layout",
     "dd3d_vovnet_conv_wgrad", "dd3d_vovnet_conv_dgrad", "dd3d_vovnet_conv_grad_slices", "dd3d_vovnet_add", "dd3d_ese_backward", "dd3d_maxpool3x3s2_ceil_backward",
-    "dd3d_vovnet_grad_layout"
+    "dd3d_vovnet_grad_layout",
+    "dd3d_bn_batch_stats", "dd3d_bn_apply_relu_split", "dd3d_bn_backward_reduce", "dd3d_bn_backward_apply", "dd3d_bn_slices", "dd3d_tower_bn_layout"
 ]
 
 
@@ -529,6 +552,11 @@ def lib():
     L.dd3d_ese_backward.argtypes = [C.POINTER(EseGradArgs), C.c_void_p]
     L.dd3d_maxpool3x3s2_ceil_backward.argtypes = [C.POINTER(Pool3GradArgs), C.c_void_p]
     L.dd3d_vovnet_grad_layout.argtypes = [C.c_void_p, C.c_int32]
+    for name in ("dd3d_bn_batch_stats", "dd3d_bn_apply_relu_split", "dd3d_bn_backward_reduce", "dd3d_bn_backward_apply"):
+        getattr(L, name).argtypes = [C.POINTER(TowerBnArgs), C.c_void_p]
+    L.dd3d_bn_slices.argtypes = [C.POINTER(TowerBnArgs)]
+    L.dd3d_bn_slices.restype = C.c_int64
+    L.dd3d_tower_bn_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

@@ -126,7 +126,7 @@ class DD3D(nn.Module):
         return plan
 
     def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False, stem_grads=False,
-                      vovnet_grads=False):
+                      vovnet_grads=False, batch_stats=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
         `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
         backward behind it as well (parameter and tower-output gradients; implies `grads`); `tower_grads`: the plan that goes on through
@@ -136,11 +136,15 @@ class DD3D(nn.Module):
         output; implies `fpn_grads`); `stem_grads`: the plan that goes on through the stem (base_layer, level0, level1: their parameter
         gradients and the gradients at base_layer's and level0's outputs; implies `backbone_grads`); `vovnet_grads`: the plan of a VoVNet-V2
         model that goes on from the FPN through stage5 .. stage2, stem_3 and stem_2 (their parameter gradients and the gradient at stem_1's
-        output; implies `fpn_grads`; a DLA model raises NotImplementedError naming `stem_grads`)."""
+        output; implies `fpn_grads`; a DLA model raises NotImplementedError naming `stem_grads`); `batch_stats`: the head towers whose norm is
+        a trainable BatchNorm2d use the batch's statistics, as the reference's train() does (composes with every level above; a plan of
+        its own beside the running-statistics one)."""
         from dd3d_amd.engine.losses import LossPlan
         level = _deepest(vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads, fpn_grads=fpn_grads, tower_grads=tower_grads,
                          pred_grads=pred_grads, grads=grads)
         key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + tuple(level)
+        if batch_stats:
+            key, level = key + ("batch_stats", ), dict(level, batch_stats=True)
         plan = self._plans.pop(key, None)
         if plan is None:
             plan = LossPlan(self, B, Hp, Wp, **level)
@@ -306,12 +310,12 @@ class DD3D(nn.Module):
     # ------------------------------------------------------------------ training losses (gradients: head maps and the predictor layer)
     @torch.no_grad()
     def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
-                       stem_grads=False, **branch):
+                       stem_grads=False, batch_stats=False, **branch):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
-        reference: every norm layer uses its running statistics (the head maps are exactly this forward's), one process
-        (reduce_sum is the identity).  With `head_grads` the result is (loss dict, grads): the gradient of the sum of the dict's values
+        reference: by default every norm layer uses its running statistics (the head maps are exactly this forward's; `batch_stats`,
+        below, gives the reference's train() forward), one process (reduce_sum is the identity).  With `head_grads` the result is (loss dict, grads): the gradient of the sum of the dict's values
         with respect to the head maps the losses read, as NCHW per-level tensors under the reference's names (logits<l>, box2d_reg<l>
         -- post-ReLU --, centerness<l>, quat<l>, ctr<l>, depth<l>, size<l>, conf<l>, attr<l>, speed<l>).  With `predictor_grads` the
         result is (loss dict, grads, param_grads): `grads` holds the same head-map gradients and also the gradient at the tower outputs
@@ -344,8 +348,15 @@ class DD3D(nn.Module):
         `stem_grads`; the slim and depthwise specs, DD3D_PLANES=0 and the reduced arithmetic modes raise too.  (`vovnet_grads` is a
         keyword of its own, not one more level of the chain head_grads .. stem_grads above, whose named parameters
         tests/test_loss_plan_history.py pins: it is taken from `**branch`, and any other extra keyword is a TypeError.)
-        The filter copies the backward reads are snapshots taken when the plan is built; there is no optimiser, no batch-statistics
-        norm and no model.train().  V2-99, the Bottleneck DLA variants, force_generic_dla and the reduced arithmetic modes raise
+        With `batch_stats` -- it composes with every flag above -- the head towers whose norm is a trainable BatchNorm2d (cls and box2d in
+        the released configs, box3d under FCOS3D.NORM: BN) normalise every layer with the batch's mean and biased variance, per pyramid
+        level and channel over the B * h_l * w_l pixels of the padded canvas, and the backward differentiates through both, as the
+        reference's train() does (csrc/tower_bn.hip); FrozenBN and norm-less towers keep the running-statistics path in the same plan.
+        Keys and shapes of every result stay, the values follow the new forward; `plan.tower_batch_stats()` (the plan of
+        `get_loss_plan(..., batch_stats=True)`) returns the running statistics the step would leave and the batch's own, and the
+        model's buffers are never written.  A level with one value per channel (one 64 x 128 image: P7 is 1 x 1) raises ValueError in
+        torch's words; FE.BACKBONE.NORM / FE.FPN.NORM = BN raise NotImplementedError naming the key.
+        The filter copies the backward reads are snapshots taken when the plan is built; there is no optimiser and no model.train().  V2-99, the Bottleneck DLA variants, force_generic_dla and the reduced arithmetic modes raise
         NotImplementedError."""
         from dd3d_amd.engine import relax_arithmetic
         vovnet_grads = bool(branch.pop("vovnet_grads", False))
@@ -358,7 +369,7 @@ class DD3D(nn.Module):
             tower_grads = tower_grads or fpn_grads
             level = _deepest(vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads, fpn_grads=fpn_grads,
                              tower_grads=tower_grads, pred_grads=predictor_grads, grads=head_grads)
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), **level)
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), batch_stats=batch_stats, **level)
             plan.stage_gt(gt)
             self.stage_inputs(batched_inputs, plan=plan)  # (its flush ships the GT too)
             plan.run()

@@ -1246,6 +1246,79 @@ int dd3d_ese_backward(const dd3d_ese_grad_args* args, void* stream);
 int dd3d_maxpool3x3s2_ceil_backward(const dd3d_pool3_grad_args* args, void* stream);
 int dd3d_vovnet_grad_layout(int64_t* out, int32_t n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batch-statistics BatchNorm of one head-tower layer, forward and backward (csrc/tower_bn.hip): what nn.BatchNorm2d computes in
+ * train() behind the tower's shared 3x3 convolution (fcos2d.py:71-93; ModuleListDial: one norm per pyramid level).  A SEGMENT is one
+ * (tower, level) pair of the layer: N = B * h * w pixels of the padded canvas, C channels, statistics per channel over the N pixels.
+ * With c the raw convolution output (f32 NHWC, conv bias included when the module has one):
+ *   mu = sum(c) / N            v = sum((c - mu)^2) / N                   two passes over c, not E[c^2] - mu^2
+ *   rstd = 1 / sqrt(v + eps)   s = gamma * rstd      t = beta - mu * s
+ *   y = relu(fmaf(c - mu, s, beta))                                        (= c * s + t without the cancellation between c * s and
+ *                                                                           mu * s: a channel constant over the batch gives relu(beta))
+ *   running_mean' = (1 - momentum) * running_mean + momentum * mu
+ *   running_var'  = (1 - momentum) * running_var  + momentum * v * N / (N - 1)       (read-outs: the inputs are never written)
+ * and with G the gradient at y, ghat = G * [stored y > 0] and xhat = (c - mu) * rstd:
+ *   q = sum(ghat)     p = sum(ghat * xhat)                               (= d beta, d gamma)
+ *   G_c = s * (ghat - q / N - xhat * p / N)                              dense: the ReLU mask does not survive
+ * Order of every sum (mu, v, q, p alike): the segment's pixels are cut into slices of DD3D_BN_SLICE consecutive pixels.  Inside a slice
+ * a channel has P = 256 / (C / 4) running sums (thread lanes); lane j adds pixels j, j + P, j + 2P, ... in that order, the lanes are
+ * added in lane order.  The slice partials (one scratch row each, one writer) are added by a second launch: eight lanes, lane j adds
+ * slices j, j + 8, ... in that order (fetched four at a time), the lanes are added in lane order.  No float atomics; two runs agree bit for bit.
+ *
+ * c, g, gc: f32 NHWC, pitches c_pitch, g_pitch, C, pointers at the segment's first channel.  stats: [DD3D_BN_STAT_ROWS][C] per segment, rows
+ *   DD3D_BN_ROW_*.  qp: [2][C] per segment (q, then p).  part: scratch [n_slices][2][C], n_slices >= dd3d_bn_slices(args) (host only; it
+ *   reads num_segs, C and N alone): sum over the segments of ceil(N / DD3D_BN_SLICE).
+ * dd3d_bn_batch_stats (four launches: slice sums, mu, slice sums of squared deviations, the rest): every word of `stats`; reads c, gamma,
+ *   beta, run_mean, run_var.
+ * dd3d_bn_apply_relu_split (one launch): y from c, beta and stats rows MU, S, as split planes of `math_mode` ([C/32][N][NP][32] 16-bit terms, first
+ *   chunk of the slice; DD3D_MATH_F16X2: halves of value * plane_scale, |value * plane_scale| > 65504 or a NaN ORs DD3D_STATUS_F16_OVERFLOW
+ *   into `status`, exactly as dd3d_split_planes) or, math_mode DD3D_MATH_F32, as f32 NHWC of pitch y_pitch.
+ * dd3d_bn_backward_reduce (two launches): qp; reads c, g, the stored y (storage y_mode, DD3D_PG_ACT_*), stats rows MU, RSTD.
+ * dd3d_bn_backward_apply (one launch): gc; reads c, g, y, qp and stats rows MU, RSTD, S.
+ * All are safe under stream capture and write nothing beyond the outputs named and the scratch rows in use.
+ * dd3d_tower_bn_layout: sizeof and field offsets (layout check of the bindings; host only).
+ * Rejected (-1, dd3d_last_error starts with the entry point's name): num_segs outside 1 .. DD3D_BN_MAX_SEGS, C not a multiple of 32 or above
+ *   DD3D_BN_MAX_C, pitches not a multiple of 4 or below C, null pointers, N < 2, too few scratch rows, unknown storages.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_BN_MAX_SEGS 24
+#define DD3D_BN_MAX_C 256
+#define DD3D_BN_SLICE 64
+#define DD3D_BN_STAT_ROWS 7
+#define DD3D_BN_ROW_MU 0
+#define DD3D_BN_ROW_VAR 1
+#define DD3D_BN_ROW_S 2
+#define DD3D_BN_ROW_T 3
+#define DD3D_BN_ROW_RSTD 4
+#define DD3D_BN_ROW_RUN_MEAN 5
+#define DD3D_BN_ROW_RUN_VAR 6
+typedef struct dd3d_tower_bn_args {         /* host memory; every pointer is device memory */
+  const float* c[DD3D_BN_MAX_SEGS];         /* raw convolution output: [N][c_pitch] */
+  const float* gamma[DD3D_BN_MAX_SEGS];     /* [C] norm weight */
+  const float* beta[DD3D_BN_MAX_SEGS];      /* [C] norm bias */
+  const float* run_mean[DD3D_BN_MAX_SEGS];  /* [C] running statistics before the step (read only) */
+  const float* run_var[DD3D_BN_MAX_SEGS];
+  float* stats[DD3D_BN_MAX_SEGS];           /* [DD3D_BN_STAT_ROWS][C] */
+  void* y[DD3D_BN_MAX_SEGS];                /* the layer's output: written by the apply, read by the backward */
+  const float* g[DD3D_BN_MAX_SEGS];         /* gradient at y: [N][g_pitch] */
+  float* qp[DD3D_BN_MAX_SEGS];              /* [2][C]: q, p */
+  float* gc[DD3D_BN_MAX_SEGS];              /* gradient at c: [N][C] */
+  float* part;                              /* scratch [n_slices][2][C] */
+  int32_t* status;                          /* DD3D_STATUS_* word, or NULL */
+  int32_t N[DD3D_BN_MAX_SEGS];              /* pixels of the segment */
+  int32_t num_segs, C, c_pitch, g_pitch;
+  int32_t math_mode;                        /* apply: DD3D_MATH_* of the planes written, DD3D_MATH_F32: f32 NHWC */
+  int32_t y_mode, y_pitch;                  /* backward: DD3D_PG_ACT_* of the stored y; floats per pixel of an f32 y (both directions) */
+  int32_t n_slices;                         /* rows of part */
+  float eps, momentum, plane_scale;         /* plane_scale: DD3D_MATH_F16X2 / DD3D_PG_ACT_F16X2 */
+  int32_t reserved;                         /* 0; ignored */
+} dd3d_tower_bn_args;
+int dd3d_bn_batch_stats(const dd3d_tower_bn_args* args, void* stream);
+int dd3d_bn_apply_relu_split(const dd3d_tower_bn_args* args, void* stream);
+int dd3d_bn_backward_reduce(const dd3d_tower_bn_args* args, void* stream);
+int dd3d_bn_backward_apply(const dd3d_tower_bn_args* args, void* stream);
+int64_t dd3d_bn_slices(const dd3d_tower_bn_args* args);
+int dd3d_tower_bn_layout(int64_t* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
