@@ -22,6 +22,12 @@
 //                        whole run of a wave.  One accumulator chain per pixel: at most 9 * 16 or 4 * 32 terms.
 // No float atomics: every sum has one writer and a fixed order that depends on the call's shape alone; two runs agree bit for bit,
 // whatever wgrad_blocks holds.
+//
+// The VoVNet-V2 stem's first convolution (vovnet.py stem_1: 3 x 3, stride 2, the four-channel image -> 64 channels) is the same weight
+// gradient at (k, s, Cin, Cout) = (3, 2, 4, 64), through entry points of its own (dd3d_vovnet_stem_wgrad / dd3d_vovnet_stem_grad_slices):
+// sg_wgrad_kernel<3, 2, 4, 64> -- one B per filter row holds its three taps kx times four channels, the fourth tap slot unused; four
+// blocks of 16 rows of Cout share it: twelve accumulator tiles a wave, 25088 bytes of LDS for the waves' meeting.  The image has no
+// gradient, so there is no input-gradient call.
 #include "act_load.h"
 #include "common.h"
 
@@ -291,21 +297,27 @@ __global__ __launch_bounds__(SG_T) void sg_dgrad_kernel(const StemK K) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ host side
-static int sg_check_shape(const dd3d_stem_grad_args* a, const char* who, bool dgrad) {
+// the shapes of one family of entry points: the DLA stem's three, or (vovnet) stem_1's one
+static int sg_check_shape(const dd3d_stem_grad_args* a, const char* who, bool dgrad, bool vovnet = false) {
   DD3D_REQUIRE(a != nullptr, "%s: null args", who);
   DD3D_REQUIRE(a->B >= 1 && a->H >= 1 && a->W >= 1, "%s: B = %d, %d x %d", who, a->B, a->H, a->W);
-  const bool base = a->ksize == 7 && a->stride == 1 && a->Cin == 4 && a->Cout == 16;
-  const bool level0 = a->ksize == 3 && a->stride == 1 && a->Cin == 16 && a->Cout == 16;
-  const bool level1 = a->ksize == 3 && a->stride == 2 && a->Cin == 16 && a->Cout == 32;
-  DD3D_REQUIRE(base || level0 || level1, "%s: (ksize, stride, Cin, Cout) = (%d, %d, %d, %d) is none of (7, 1, 4, 16), (3, 1, 16, 16), (3, 2, 16, 32)", who,
-               a->ksize, a->stride, a->Cin, a->Cout);
-  DD3D_REQUIRE(!(dgrad && base), "%s: the 7 x 7 on the image has no input gradient", who);
+  if (vovnet) {
+    DD3D_REQUIRE(a->ksize == 3 && a->stride == 2 && a->Cin == 4 && a->Cout == 64, "%s: (ksize, stride, Cin, Cout) = (%d, %d, %d, %d) is not (3, 2, 4, 64)", who,
+                 a->ksize, a->stride, a->Cin, a->Cout);
+  } else {
+    const bool base = a->ksize == 7 && a->stride == 1 && a->Cin == 4 && a->Cout == 16;
+    const bool level0 = a->ksize == 3 && a->stride == 1 && a->Cin == 16 && a->Cout == 16;
+    const bool level1 = a->ksize == 3 && a->stride == 2 && a->Cin == 16 && a->Cout == 32;
+    DD3D_REQUIRE(base || level0 || level1, "%s: (ksize, stride, Cin, Cout) = (%d, %d, %d, %d) is none of (7, 1, 4, 16), (3, 1, 16, 16), (3, 2, 16, 32)", who,
+                 a->ksize, a->stride, a->Cin, a->Cout);
+    DD3D_REQUIRE(!(dgrad && base), "%s: the 7 x 7 on the image has no input gradient", who);
+  }
   DD3D_REQUIRE((long)a->B * a->H * a->W <= DD3D_BG_MAX_PIXELS, "%s: %ld input pixels (at most %ld)", who, (long)a->B * a->H * a->W, (long)DD3D_BG_MAX_PIXELS);
   return DD3D_OK;
 }
 
-static int sg_check_args(const dd3d_stem_grad_args* a, const char* who, bool dgrad) {
-  const int rc = sg_check_shape(a, who, dgrad);
+static int sg_check_args(const dd3d_stem_grad_args* a, const char* who, bool dgrad, bool vovnet = false) {
+  const int rc = sg_check_shape(a, who, dgrad, vovnet);
   if (rc != DD3D_OK) return rc;
   DD3D_REQUIRE(a->g && a->w && a->scale && a->y, "%s: no gradient / filter / scale / stored output", who);
   DD3D_REQUIRE(a->g_pitch % 4 == 0 && a->g_pitch >= a->Cout, "%s: g_pitch = %d must be a multiple of 4 and hold %d channels", who, a->g_pitch, a->Cout);
@@ -334,19 +346,22 @@ extern "C" int64_t dd3d_stem_grad_slices(const dd3d_stem_grad_args* args) {
   return k.nslices;
 }
 
-extern "C" int dd3d_stem_wgrad(const dd3d_stem_grad_args* args, void* stream) {
-  using namespace dd3d;
-  const int rc = sg_check_args(args, "dd3d_stem_wgrad", false);
+namespace dd3d {
+
+// the weight gradient's three launches for either family of entry points
+static int sg_run_wgrad(const dd3d_stem_grad_args* args, void* stream, const char* who, bool vovnet) {
+  const int rc = sg_check_args(args, who, false, vovnet);
   if (rc != DD3D_OK) return rc;
-  DD3D_REQUIRE(args->dw_level && args->dw && args->q && args->r, "dd3d_stem_wgrad: null output");
+  DD3D_REQUIRE(args->dw_level && args->dw && args->q && args->r, "%s: null output", who);
   StemK k;
   plan_stem(*args, k);
-  DD3D_REQUIRE(args->part && args->qpart && args->n_slices >= k.nslices, "dd3d_stem_wgrad: part / qpart (%d slices for %d)", args->n_slices, k.nslices);
-  DD3D_REQUIRE(args->wgrad_blocks >= 0, "dd3d_stem_wgrad: wgrad_blocks = %d", args->wgrad_blocks);
+  DD3D_REQUIRE(args->part && args->qpart && args->n_slices >= k.nslices, "%s: part / qpart (%d slices for %d)", who, args->n_slices, k.nslices);
+  DD3D_REQUIRE(args->wgrad_blocks >= 0, "%s: wgrad_blocks = %d", who, args->wgrad_blocks);
   const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int KK = args->ksize * args->ksize * args->Cin;
   const dim3 grid((unsigned)(args->wgrad_blocks > 0 && args->wgrad_blocks < k.nslices ? args->wgrad_blocks : k.nslices));
-  if (args->ksize == 7) hipLaunchKernelGGL((sg_wgrad_kernel<7, 1, 4, 16>), grid, dim3(SG_T), 0, s, k);
+  if (vovnet) hipLaunchKernelGGL((sg_wgrad_kernel<3, 2, 4, 64>), grid, dim3(SG_T), 0, s, k);
+  else if (args->ksize == 7) hipLaunchKernelGGL((sg_wgrad_kernel<7, 1, 4, 16>), grid, dim3(SG_T), 0, s, k);
   else if (args->stride == 1) hipLaunchKernelGGL((sg_wgrad_kernel<3, 1, 16, 16>), grid, dim3(SG_T), 0, s, k);
   else hipLaunchKernelGGL((sg_wgrad_kernel<3, 2, 16, 32>), grid, dim3(SG_T), 0, s, k);
   int e = check_launch("sg_wgrad_kernel");
@@ -355,6 +370,22 @@ extern "C" int dd3d_stem_wgrad(const dd3d_stem_grad_args* args, void* stream) {
   if ((e = check_launch("sg_wreduce_kernel")) != DD3D_OK) return e;
   hipLaunchKernelGGL(sg_rsum_kernel, dim3((unsigned)args->Cout), dim3(SG_T), 0, s, k, KK);
   return check_launch("sg_rsum_kernel");
+}
+
+}  // namespace dd3d
+
+extern "C" int dd3d_stem_wgrad(const dd3d_stem_grad_args* args, void* stream) { return dd3d::sg_run_wgrad(args, stream, "dd3d_stem_wgrad", false); }
+
+extern "C" int64_t dd3d_vovnet_stem_grad_slices(const dd3d_stem_grad_args* args) {
+  using namespace dd3d;
+  if (sg_check_shape(args, "dd3d_vovnet_stem_grad_slices", false, true) != DD3D_OK) return -1;
+  StemK k;
+  plan_stem(*args, k);
+  return k.nslices;
+}
+
+extern "C" int dd3d_vovnet_stem_wgrad(const dd3d_stem_grad_args* args, void* stream) {
+  return dd3d::sg_run_wgrad(args, stream, "dd3d_vovnet_stem_wgrad", true);
 }
 
 extern "C" int dd3d_stem_dgrad(const dd3d_stem_grad_args* args, void* stream) {

@@ -5,8 +5,9 @@ their parameters and the FPN outputs (csrc/tower_grads.hip), and one stage furth
 output features (csrc/fpn_grads.hip), and one stage further again through the DLA-34 backbone's level5 .. level2 to their parameters
 and the stem's output (csrc/backbone_grads.hip), and last through the stem -- base_layer, level0, level1 -- to its parameters
 (csrc/stem_grads.hip); for the VoVNet-V2 backbones, behind the FPN through stage5 .. stage2, stem_3 and stem_2 (csrc/vovnet_grads.hip and
-the wide entry points of csrc/backbone_grads.hip).  With batch_stats=True the head towers whose norm is a trainable
-BatchNorm2d use the batch's statistics, forward and backward (csrc/tower_bn.hip).  There is no optimiser or model.train().
+the wide entry points of csrc/backbone_grads.hip) and last stem_1's filter (dd3d_vovnet_stem_wgrad, csrc/stem_grads.hip).  With
+batch_stats=True the head towers whose norm is a trainable BatchNorm2d use the batch's statistics, forward and backward
+(csrc/tower_bn.hip).  There is no optimiser or model.train().
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -571,6 +572,40 @@ class StemConvGrads(GradCall):
             self.da = self.out(B, self.H, self.W, Cin) if da is None else da
             assert tuple(self.da.shape) == (B, self.H, self.W, Cin) and self.da.stride(-1) == 1
             a.da, a.da_pitch = self.da.data_ptr(), pitch(self.da)
+        a.y, a.y_mode, a.y_pitch, a.y_plane_scale = y[1] or None, int(y[0]), int(y[2]), float(y[3])
+        a.g, a.w, a.scale, a.g_pitch = g.data_ptr(), w.data_ptr(), scale.data_ptr(), pitch(g)
+        a.B, a.H, a.W, a.Cin, a.Cout, a.ksize, a.stride = int(B), self.H, self.W, int(Cin), int(Cout), int(ksize), int(stride)
+        a.n_slices, a.wgrad_blocks = self.n_slices, int(wgrad_blocks)
+        self.args = a
+
+
+class VovnetStemGrads(GradCall):
+    """Buffers and dd3d_stem_grad_args of the VoVNet-V2 stem_1's weight gradient (dd3d_vovnet_stem_wgrad, csrc/stem_grads.hip):
+    (ksize, stride, Cin, Cout) = hip.VOVNET_STEM_GRAD_SHAPE.  There is no input gradient: the image has none.
+
+    `H`, `W`: the INPUT's sizes; `x`: [B, H, W, 4] f32 normalised image, possibly a channel slice of a wider tensor; `y`: (mode, device
+    address, pitch, plane scale) of stem_1's stored output, whose ReLU the gradient crosses; `g`: [B, Ho, Wo, 64] f32 gradient at that
+    output (a slice may be given); `w`: [64, 3, 3, 4]; `scale`: [64]; `slab`: (part, qpart) shared with other calls that run in stream
+    order, or None to allocate them; `wgrad_blocks`: blocks of the main launch (0: one per slice).  Outputs are allocated here, filled
+    with `fill` and followed by `guard` words of it."""
+    ENTRIES = (("dd3d_vovnet_stem_wgrad", "vovnet_stem_wgrad"), )
+    with_dgrad = False
+
+    def __init__(self, device, B, H, W, x, y, g, w, scale, slab=None, fill=0.0, guard=0, wgrad_blocks=0):
+        GradCall.__init__(self, device, fill, guard)
+        ksize, stride, Cin, Cout = hip.VOVNET_STEM_GRAD_SHAPE
+        self.B, self.H, self.W, self.Cin, self.Cout, self.ksize, self.stride = B, int(H), int(W), Cin, Cout, ksize, stride
+        self.Ho, self.Wo = (self.H + stride - 1) // stride, (self.W + stride - 1) // stride
+        self.keep = (x, g, w, scale, slab)
+        self.scale = scale
+        a = hip.StemGradArgs()
+        pitch = self.pitch
+        assert tuple(g.shape) == (B, self.Ho, self.Wo, Cout) and g.stride(-1) == 1, (tuple(g.shape), (B, self.Ho, self.Wo, Cout))
+        assert tuple(x.shape) == (B, self.H, self.W, Cin) and x.stride(-1) == 1, (tuple(x.shape), (B, self.H, self.W, Cin))
+        assert tuple(w.shape) == (Cout, ksize, ksize, Cin) and w.is_contiguous(), tuple(w.shape)
+        self.n_slices = hip.vovnet_stem_grad_slices(B, self.H, self.W)
+        self.wgrad_outputs(a, slab, Cout, ksize * ksize * Cin)
+        a.x, a.x_pitch = x.data_ptr(), pitch(x)
         a.y, a.y_mode, a.y_pitch, a.y_plane_scale = y[1] or None, int(y[0]), int(y[2]), float(y[3])
         a.g, a.w, a.scale, a.g_pitch = g.data_ptr(), w.data_ptr(), scale.data_ptr(), pitch(g)
         a.B, a.H, a.W, a.Cin, a.Cout, a.ksize, a.stride = int(B), self.H, self.W, int(Cin), int(Cout), int(ksize), int(stride)
@@ -1148,11 +1183,12 @@ class LossPlan(ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
     def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
-                 fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False, batch_stats=False):
+                 fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False):
         self.batch_stats = bool(batch_stats)
         if self.batch_stats:  # before anything is built or launched
             check_batch_stats(model, B, Hp, Wp)
-        self.with_vovnet_grads = bool(vovnet_grads)  # (`vovnet_grads` itself is the read-out method)
+        self.with_vovnet_stem_grads = bool(vovnet_stem_grads)  # (`vovnet_stem_grads` itself is the read-out method)
+        self.with_vovnet_grads = bool(vovnet_grads) or self.with_vovnet_stem_grads  # (`vovnet_grads` itself is the read-out method)
         if self.with_vovnet_grads:  # before anything is built or launched
             check_vovnet_backward(model.backbone.bottom_up, model)
         self.with_stem_grads = bool(stem_grads)  # (read by the trunk: the stem keeps its intermediates and the normalised image)
@@ -1240,6 +1276,8 @@ class LossPlan(ForwardPlan):
             self._stem_grads(model)
         if self.with_vovnet_grads:
             self._vovnet_grads(model)
+        if self.with_vovnet_stem_grads:
+            self._vovnet_stem_grads(model)
 
     def _loss_grads(self, a):
         """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
@@ -1544,8 +1582,8 @@ class LossPlan(ForwardPlan):
         """The VoVNet-V2 backbone's backward behind the FPN's (include/dd3d_hip.h states it; `vovnet_backward` lays out the calls): stage5
         down to stage2, then stem_3 and stem_2 -- per OSA module one eSE call (four launches), one weight-gradient and one input-gradient
         call per convolution, one elementwise sum under `identity`, one launch per 3x3 max-pool -- on the main stream, still one hipGraph.  The chain ends at the gradient of
-        stem_1's stored output; stem_1's filter has no gradient.  Every call shares the one slab of weight-gradient partials, sized for
-        its largest user."""
+        stem_1's stored output; LossPlan(vovnet_stem_grads=True) goes on from there (_vovnet_stem_grads).  Every call shares the one slab
+        of weight-gradient partials, sized for its largest user."""
         dev, B = self.device, self.B
         vov = model.backbone.bottom_up
         if not self.use_planes:
@@ -1568,10 +1606,45 @@ class LossPlan(ForwardPlan):
     def vovnet_grads(self):
         """(the gradient at stem_1's stored output, VoVNet parameter gradients) of the last run, copies: {backbone_stem_1: (B, 64, Hp / 2,
         Wp / 2)} -- not yet masked by that tensor's own ReLU -- and {name in model.named_parameters(): tensor of the parameter's shape} for
-        every parameter of backbone.bottom_up but stem.stem_1/*, float32."""
+        every parameter of backbone.bottom_up but stem.stem_1/* (those: vovnet_stem_grads), float32."""
         if not self.with_vovnet_grads:
             raise RuntimeError("this LossPlan was built without vovnet_grads=True")
         return {"backbone_stem_1": self.stem1_grad.permute(0, 3, 1, 2).clone()}, vovnet_param_grads(self._named(), self.vovnet_layers)
+
+    def _vovnet_stem_grads(self, model):
+        """stem_1's backward behind stem_2's (dd3d_vovnet_stem_wgrad, csrc/stem_grads.hip; include/dd3d_hip.h states it): ONE
+        weight-gradient call on the main stream -- still one hipGraph; the image has no gradient.  It reads the f32 normalised image
+        `img4` (pitch 4, fourth channel zero), takes the ReLU mask from the stored `stem.0` and the incoming gradient from stem_2's input
+        gradient.  The call shares the plan's slab of weight-gradient partials; it never grows for it (a slice is 64 x 36 words)."""
+        from dd3d_amd.layers import fold_norm
+        dev, B = self.device, self.B
+        vov = model.backbone.bottom_up
+        cname, nname, _ = vov.stem_seqs[0]
+        conv, norm = getattr(vov.stem, cname), getattr(vov.stem, nname)
+        xb, yv = self.bufs["img4"], self.bufs["stem.0"].view()
+        k, stride, cin, cout = hip.VOVNET_STEM_GRAD_SHAPE
+        shape = (int(conv.weight.shape[-1]), int(conv.stride), int(xb.pitch), int(conv.weight.shape[0]))
+        assert shape == (k, stride, cin, cout) and xb.has_f32 and xb.t is not None and yv.C == cout, (cname, shape)
+        part, qpart = self.tower_slab
+        n = hip.vovnet_stem_grad_slices(B, xb.H, xb.W)
+        assert n * cout * k * k * cin <= part.numel() and n * cout <= qpart.numel(), \
+            f"vovnet_stem_grads.stem_1: {n} slices of {cout} x {k * k * cin} words do not fit the plan's slab of {part.numel()} words"
+        w = filter_copy(conv, dev, cin)  # (the image's fourth channel: a zero filter)
+        lay = VovnetStemGrads(dev, B, xb.H, xb.W, xb.t, act_binding(self, yv), self.stem1_grad, w, self._vec(fold_norm(conv, norm)[0]), slab=self.tower_slab)
+        lay.conv, lay.norm, lay.src = conv, norm, dict(x=("img4", 0, cin), y=("stem.0", 0, cout))
+        self.vovnet_stem_layers = OrderedDict(stem_1=lay)
+        self._append_calls("vovnet_stem_grads", self.vovnet_stem_layers)
+        self.vovnet_stem_reads = self._check_reads("VoVNet stem", [xb.view(), yv])
+
+    def vovnet_stem_grads(self):
+        """(nothing, stem_1's parameter gradients) of the last run, copies: {} -- the image has no gradient -- and {name in
+        model.named_parameters(): tensor of the parameter's shape} for backbone.bottom_up.stem.stem_1/conv.weight ((64, 3, 3, 3): the pad
+        channel's column is dropped) and, for a BN backbone on running statistics, stem.stem_1/norm.weight and .bias; FrozenBN owns
+        nothing.  With vovnet_grads' these are the parameters of named_parameters()."""
+        if not self.with_vovnet_stem_grads:
+            raise RuntimeError("this LossPlan was built without vovnet_stem_grads=True")
+        lay = self.vovnet_stem_layers["stem_1"]
+        return {}, conv_param_grads(self._named(), lay, lay.conv, lay.norm, lay.dw, lay.scale, lay.q, lay.r)
 
     def tower_grads(self):
         """(FPN-output gradients, tower parameter gradients) of the last run, copies: {feature<l>: (B, C, h_l, w_l)} and {name in

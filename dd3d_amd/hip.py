@@ -375,6 +375,7 @@ def ese_grad_rsplit(HW):
 
 SG_UNIT, SG_TARGET_SLICES, SG_MIN_UNITS_PER_SLICE, SG_MAX_UNITS_PER_SLICE = 64, 512, 8, 64
 STEM_GRAD_SHAPES = ((7, 1, 4, 16), (3, 1, 16, 16), (3, 2, 16, 32))  # (ksize, stride, Cin, Cout) of base_layer, level0.0, level1.0
+VOVNET_STEM_GRAD_SHAPE = (3, 2, 4, 64)  # (ksize, stride, Cin, Cout) of the VoVNet-V2 stem_1 (dd3d_vovnet_stem_wgrad)
 
 
 class StemGradArgs(C.Structure):
@@ -399,6 +400,13 @@ def stem_grad_slices(B, H, W, Cin, Cout, ksize, stride):
     if ups * max_slices < units:
         ups = (units + max_slices - 1) // max_slices
     return (units + ups - 1) // ups
+
+
+def vovnet_stem_grad_slices(B, H, W):
+    """Rows of `part` / `qpart` one dd3d_vovnet_stem_wgrad call needs (the rule of dd3d_vovnet_stem_grad_slices -- stem_grad_slices' at
+    VOVNET_STEM_GRAD_SHAPE --, for plans built without a device).  H, W: the INPUT's sizes."""
+    ksize, stride, Cin, Cout = VOVNET_STEM_GRAD_SHAPE
+    return stem_grad_slices(B, H, W, Cin, Cout, ksize, stride)
 
 
 BN_MAX_SEGS, BN_MAX_C, BN_SLICE, BN_STAT_ROWS = 24, 256, 64, 7
@@ -436,6 +444,7 @@ EXPORTS = [
     "dd3d_fpn_wgrad", "dd3d_fpn_dgrad", "dd3d_fpn_grad_slices", "dd3d_fpn_grad_layout",
     "dd3d_backbone_wgrad", "dd3d_backbone_dgrad", "dd3d_backbone_grad_slices", "dd3d_maxpool2x2_backward", "dd3d_backbone_grad_layout",
     "dd3d_stem_wgrad", "dd3d_stem_dgrad", "dd3d_stem_grad_slices", "dd3d_stem_grad_layout",
+    "dd3d_vovnet_stem_wgrad", "dd3d_vovnet_stem_grad_slices",
     "dd3d_vovnet_conv_wgrad", "dd3d_vovnet_conv_dgrad", "dd3d_vovnet_conv_grad_slices", "dd3d_vovnet_add", "dd3d_ese_backward", "dd3d_maxpool3x3s2_ceil_backward",
     "dd3d_vovnet_grad_layout",
     "dd3d_bn_batch_stats", "dd3d_bn_apply_relu_split", "dd3d_bn_backward_reduce", "dd3d_bn_backward_apply", "dd3d_bn_slices", "dd3d_tower_bn_layout"
@@ -544,6 +553,9 @@ def lib():
     L.dd3d_stem_grad_slices.argtypes = [C.POINTER(StemGradArgs)]
     L.dd3d_stem_grad_slices.restype = C.c_int64
     L.dd3d_stem_grad_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_vovnet_stem_wgrad.argtypes = [C.POINTER(StemGradArgs), C.c_void_p]
+    L.dd3d_vovnet_stem_grad_slices.argtypes = [C.POINTER(StemGradArgs)]
+    L.dd3d_vovnet_stem_grad_slices.restype = C.c_int64
     L.dd3d_vovnet_conv_wgrad.argtypes = [C.POINTER(BackboneGradArgs), C.c_void_p]
     L.dd3d_vovnet_conv_dgrad.argtypes = [C.POINTER(BackboneGradArgs), C.c_void_p]
     L.dd3d_vovnet_conv_grad_slices.argtypes = [C.POINTER(BackboneGradArgs)]

@@ -126,7 +126,7 @@ class DD3D(nn.Module):
         return plan
 
     def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False, stem_grads=False,
-                      vovnet_grads=False, batch_stats=False):
+                      vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
         `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
         backward behind it as well (parameter and tower-output gradients; implies `grads`); `tower_grads`: the plan that goes on through
@@ -136,12 +136,14 @@ class DD3D(nn.Module):
         output; implies `fpn_grads`); `stem_grads`: the plan that goes on through the stem (base_layer, level0, level1: their parameter
         gradients and the gradients at base_layer's and level0's outputs; implies `backbone_grads`); `vovnet_grads`: the plan of a VoVNet-V2
         model that goes on from the FPN through stage5 .. stage2, stem_3 and stem_2 (their parameter gradients and the gradient at stem_1's
-        output; implies `fpn_grads`; a DLA model raises NotImplementedError naming `stem_grads`); `batch_stats`: the head towers whose norm is
+        output; implies `fpn_grads`; a DLA model raises NotImplementedError naming `stem_grads`); `vovnet_stem_grads`: the plan that goes on
+        through stem_1 (its parameter gradients; the image has no gradient; implies `vovnet_grads`, and raises for whatever that raises for);
+        `batch_stats`: the head towers whose norm is
         a trainable BatchNorm2d use the batch's statistics, as the reference's train() does (composes with every level above; a plan of
         its own beside the running-statistics one)."""
         from dd3d_amd.engine.losses import LossPlan
-        level = _deepest(vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads, fpn_grads=fpn_grads, tower_grads=tower_grads,
-                         pred_grads=pred_grads, grads=grads)
+        level = _deepest(vovnet_stem_grads=vovnet_stem_grads, vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads,
+                         fpn_grads=fpn_grads, tower_grads=tower_grads, pred_grads=pred_grads, grads=grads)
         key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + tuple(level)
         if batch_stats:
             key, level = key + ("batch_stats", ), dict(level, batch_stats=True)
@@ -344,10 +346,14 @@ class DD3D(nn.Module):
         stem_1's stored output, (B, 64, Hp / 2, Wp / 2), not yet masked by that tensor's own ReLU -- and `param_grads` also every
         parameter of backbone.bottom_up except stem.stem_1/* (each OSA module's layers.<i>.<n>_<i>/conv.weight, concat.<n>_concat/conv.weight,
         ese.fc.weight and ese.fc.bias; stem.stem_2/conv.weight and stem.stem_3/conv.weight; a BN backbone's norm weights and biases).
-        stem_1's filter (3x3 stride 2 on the four-channel image) has no gradient yet.  DLA models raise NotImplementedError naming
-        `stem_grads`; the slim and depthwise specs, DD3D_PLANES=0 and the reduced arithmetic modes raise too.  (`vovnet_grads` is a
-        keyword of its own, not one more level of the chain head_grads .. stem_grads above, whose named parameters
-        tests/test_loss_plan_history.py pins: it is taken from `**branch`, and any other extra keyword is a TypeError.)
+        With `vovnet_stem_grads` the result has the same form and the backward goes on through stem_1 (3x3 stride 2 on the four-channel
+        image; the image itself has no gradient): everything `vovnet_grads` returns, bit for bit (backbone_stem_1 included, still
+        unmasked), and `param_grads` also holds backbone.bottom_up.stem.stem_1/conv.weight ((64, 3, 3, 3)) and a BN backbone's
+        stem.stem_1/norm.weight / .bias: for the four covered VoVNet specs its keys are then those of named_parameters().  DLA models
+        raise NotImplementedError naming `stem_grads`; the slim and depthwise specs, DD3D_PLANES=0 and the reduced arithmetic modes raise
+        too.  (`vovnet_grads` and `vovnet_stem_grads` are keywords of their own, not further levels of the chain head_grads .. stem_grads
+        above, whose named parameters tests/test_loss_plan_history.py pins: they are taken from `**branch`, and any other extra keyword is
+        a TypeError.)
         With `batch_stats` -- it composes with every flag above -- the head towers whose norm is a trainable BatchNorm2d (cls and box2d in
         the released configs, box3d under FCOS3D.NORM: BN) normalise every layer with the batch's mean and biased variance, per pyramid
         level and channel over the B * h_l * w_l pixels of the padded canvas, and the backward differentiates through both, as the
@@ -359,7 +365,8 @@ class DD3D(nn.Module):
         The filter copies the backward reads are snapshots taken when the plan is built; there is no optimiser and no model.train().  V2-99, the Bottleneck DLA variants, force_generic_dla and the reduced arithmetic modes raise
         NotImplementedError."""
         from dd3d_amd.engine import relax_arithmetic
-        vovnet_grads = bool(branch.pop("vovnet_grads", False))
+        vovnet_stem_grads = bool(branch.pop("vovnet_stem_grads", False))
+        vovnet_grads = bool(branch.pop("vovnet_grads", False)) or vovnet_stem_grads
         if branch:
             raise TypeError(f"compute_losses() got an unexpected keyword argument {next(iter(branch))!r}")
         gt = [x["instances"] for x in batched_inputs]
@@ -367,8 +374,8 @@ class DD3D(nn.Module):
             backbone_grads = backbone_grads or stem_grads
             fpn_grads = fpn_grads or backbone_grads or vovnet_grads
             tower_grads = tower_grads or fpn_grads
-            level = _deepest(vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads, fpn_grads=fpn_grads,
-                             tower_grads=tower_grads, pred_grads=predictor_grads, grads=head_grads)
+            level = _deepest(vovnet_stem_grads=vovnet_stem_grads, vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads,
+                             fpn_grads=fpn_grads, tower_grads=tower_grads, pred_grads=predictor_grads, grads=head_grads)
             plan = self.get_loss_plan(*self.canvas_size(batched_inputs), batch_stats=batch_stats, **level)
             plan.stage_gt(gt)
             self.stage_inputs(batched_inputs, plan=plan)  # (its flush ships the GT too)
@@ -384,7 +391,7 @@ class DD3D(nn.Module):
             if predictor_grads or tower_grads:
                 towers, params = plan.predictor_grads()
                 for on, read in ((tower_grads, plan.tower_grads), (fpn_grads, plan.fpn_grads), (backbone_grads, plan.backbone_grads),
-                                 (stem_grads, plan.stem_grads), (vovnet_grads, plan.vovnet_grads)):
+                                 (stem_grads, plan.stem_grads), (vovnet_grads, plan.vovnet_grads), (vovnet_stem_grads, plan.vovnet_stem_grads)):
                     if on:
                         tens, more = read()
                         towers, params = dict(towers, **tens), dict(params, **more)

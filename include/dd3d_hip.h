@@ -1149,10 +1149,26 @@ int dd3d_stem_wgrad(const dd3d_stem_grad_args* args, void* stream);
 int dd3d_stem_dgrad(const dd3d_stem_grad_args* args, void* stream);
 int64_t dd3d_stem_grad_slices(const dd3d_stem_grad_args* args);
 int dd3d_stem_grad_layout(int64_t* out, int32_t n);
+/* The VoVNet-V2 stem's first convolution (vovnet.py stem_1: 3 x 3, stride 2, padding 1, the normalised four-channel image -> 64 channels,
+ * folded norm, ReLU) has the same weight gradient through entry points of its own, on the same struct (layout unchanged):
+ *   shape    (ksize, stride, Cin, Cout) = (3, 2, 4, 64) alone.  There is no input gradient: the image has none.
+ * The contract is dd3d_stem_wgrad's, word for word: exact f32 products on v_mfma_f32_16x16x4_f32; g masked by the stored output y (any
+ * DD3D_PG_ACT_* storage) while it is loaded; per-slice partials in `part` / `qpart`; the slicing depends on the shape alone -- units of up
+ * to DD3D_SG_UNIT output pixels of a row, the same target / minimum / maximum / slab rule (dd3d_vovnet_stem_grad_slices); the four waves
+ * added as (0 + 2) + (1 + 3); the slices summed in slice order, 64 to a sub-sum; dw_level, dw = scale * dw_level, q and r as above.  A B
+ * operand holds the three taps kx of a filter row times four channels, the fourth tap slot unused; dw's column of channel 3 is computed
+ * like the others.  No float atomics, one writer per word: two runs agree bit for bit, whatever wgrad_blocks holds.  Every word of
+ * dw_level, dw, q and r is written; nothing beyond them and the slab rows in use.  Three launches.  Safe under stream capture.
+ * dd3d_vovnet_stem_grad_slices: host only, reads B, H, W, Cin, Cout, ksize, stride.
+ * Rejected (-1, dd3d_last_error starts with the entry point's name): any other (ksize, stride, Cin, Cout) -- the DLA stem's three shapes
+ *   included, as dd3d_stem_wgrad / dd3d_stem_grad_slices keep rejecting this one --, pitches not a multiple of 4 or too small, an unknown
+ *   y storage, null pointers, too few slab rows, a negative wgrad_blocks, more than DD3D_BG_MAX_PIXELS input pixels. */
+int dd3d_vovnet_stem_wgrad(const dd3d_stem_grad_args* args, void* stream);
+int64_t dd3d_vovnet_stem_grad_slices(const dd3d_stem_grad_args* args);
 
 /* ------------------------------------------------------------------------------------------------
- * Backward of the VoVNet-V2 backbone, stage5 down to stem_2 (csrc/vovnet_grads.hip; the wide convolution entry points live beside the
- * kernels they launch in csrc/backbone_grads.hip): the specs whose channel counts are multiples of 32 (V-19-eSE, V-39-eSE, V-57-eSE,
+ * Backward of the VoVNet-V2 backbone, stage5 down to stem_1 (csrc/vovnet_grads.hip; stem_1's call: csrc/stem_grads.hip, above; the wide
+ * convolution entry points live beside the kernels they launch in csrc/backbone_grads.hip): the specs whose channel counts are multiples of 32 (V-19-eSE, V-39-eSE, V-57-eSE,
  * V-99-eSE; vovnet.py:188-273; BackboneLowering._vovnet).  n(.), the ReLU masks and G_t as in the DLA section.  One OSA module with input
  * x, concat buffer cat = [x | l0 | .. | l(n-1)], pre-eSE tensor xt and output `out`:
  *   op        forward                                       backward
@@ -1168,7 +1184,9 @@ int dd3d_stem_grad_layout(int64_t* out, int32_t n);
  *   max-pool  x = maxpool3x3s2_ceil(prev stage's out)       G_prev_out = F_prev_out + the gathered window gradients (dd3d_maxpool3x3s2_ceil_backward)
  *   stem_3    cat2[x] = relu(n(conv3x3_s2(stem_2 out)))     dW = wgrad([x > 0] G_x, stem_2 out), G_stem2 = dgrad_s2([x > 0] G_x, W)
  *   stem_2    stem_2 out = relu(n(conv3x3(stem_1 out)))     dW = wgrad([. > 0] G_stem2, stem_1 out), G_stem1 = dgrad(.) -- not masked by stem_1's
- *                                                           own ReLU; stem_1's filter has no gradient here
+ *                                                           own ReLU
+ *   stem_1    stem_1 out = relu(n(conv3x3_s2(image)))       dW = wgrad([stem_1 out > 0] G_stem1, image) (dd3d_vovnet_stem_wgrad above); the image
+ *                                                           has no gradient
  * F_t: the FPN's gradient at a stage output.  The order of every sum is the order written here; none uses float atomics.
  *
  * dd3d_vovnet_conv_wgrad / dd3d_vovnet_conv_dgrad / dd3d_vovnet_conv_grad_slices: dd3d_backbone_wgrad / dd3d_backbone_dgrad /
