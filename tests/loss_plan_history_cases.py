@@ -16,11 +16,23 @@ from tests import whole_model_grad_oracle as WO
 # compute_losses' flags, shallowest first, with the flag DD3D.get_loss_plan knows the same plan by
 LEVELS = [(None, None), ("head_grads", "grads"), ("predictor_grads", "pred_grads"), ("tower_grads", "tower_grads"), ("fpn_grads", "fpn_grads"),
           ("backbone_grads", "backbone_grads"), ("stem_grads", "stem_grads")]
-PLAN_FLAG = dict(LEVELS)
+# a VoVNet-V2 model's ladder: the shared levels up to the FPN, then the two flags compute_losses takes from **branch
+V99_LEVELS = LEVELS[:5] + [("vovnet_grads", "vovnet_grads"), ("vovnet_stem_grads", "vovnet_stem_grads")]
+PLAN_FLAG = dict(LEVELS + V99_LEVELS)
 
-# `case`: the case of WO.CASES whose model, weights, canvas and first batch the sequence uses; `deepest`: the flag the references are
-# computed at; `steps`: the labels in order; `batches`: label -> dict(pixels: make_inputs' seed, sizes: per-image (h, w) or None for the
-# canvas', gt_seed, n_per_image, empty: images without GT), or "case" for the whole-model case's own batch.
+# `case`: the case of WO.CASES whose model, weights, canvas and first batch the sequence uses, or a dict of that form of the sequence's
+# own; `deepest`: the flag the references are computed at; `steps`: the labels in order; `batches`: label -> dict(pixels: make_inputs'
+# seed, sizes: per-image (h, w) or None for the canvas', gt_seed, n_per_image, empty: images without GT), or "case" for the whole-model
+# case's own batch; `extra`: further keywords of compute_losses and get_loss_plan (batch_stats), for the replayed model and the fresh
+# references alike.
+_V99_B2 = dict(WO.CASES["kitti_v99"], B=2)  # two images on the 128 x 256 canvas: the eSE mean and the ceil_mode pool read the padding
+# GT seeds of the V2-99 batches: scanned on the CPU (2100 .. 2105 for A and for B: every pair but (2105, 2101) meets
+# the conditions tests/test_loss_plan_history.py asserts; on this canvas positives fall on the three finest levels only)
+_V99_B2_BATCHES = {
+    "A": dict(pixels=1000, sizes=[None, None], gt_seed=2100, n_per_image=24, empty=()),                              # 24 boxes per image
+    "B": dict(pixels=1100, sizes=[None, (101, 189)], gt_seed=2103, n_per_image=24, empty=(1, )),                    # no stride divides 101 x 189
+    "C": dict(pixels=1200, sizes=[None, None], gt_seed=2000, n_per_image=0, empty=(0, 1)),                          # num_pos = 0
+}
 SEQUENCES = {
     "kitti_dla34": dict(
         case="kitti_dla34", deepest="stem_grads", steps=["A", "B", "C", "D", "A"], zero_positives=("C", ), many_positives=("A", "D"),
@@ -42,7 +54,15 @@ SEQUENCES = {
             "A": "case",                                                                                            # seed 2000
             "B": dict(pixels=1100, sizes=[None], gt_seed=2000, n_per_image=0, empty=(0, )),
         }),
+    # the VoVNet backward (OSA, eSE, 3x3 pool, stem_1) with a second image to pad
+    "kitti_v99_b2": dict(case=_V99_B2, deepest="vovnet_stem_grads", steps=["A", "B", "C", "A"], zero_positives=("C", ), many_positives=("A", "B"),
+                         batches=_V99_B2_BATCHES),
+    "kitti_v99_b2_bn": dict(case=_V99_B2, deepest="vovnet_stem_grads", extra=dict(batch_stats=True), steps=["A", "B", "A"], zero_positives=(),
+                            many_positives=("A", "B"), batches={k: _V99_B2_BATCHES[k] for k in "AB"}),
 }
+# batch statistics in the towers sum over the whole padded canvas: the DLA sequences again, batch for batch
+SEQUENCES["kitti_dla34_bn"] = dict(SEQUENCES["kitti_dla34"], extra=dict(batch_stats=True))
+SEQUENCES["nusc_dla34_bn"] = dict(SEQUENCES["nusc_dla34"], extra=dict(batch_stats=True))
 # part 4 (the range guard's retry loop inside compute_losses): dd3d_kitti_dla34 on 1 x 128 x 256 with GT
 # GT seed: scanned like the whole-model cases' for a batch without a positive near a non-smooth point of the loss (seeds 2000, 2001 and
 # 2004 .. 2006 have one such positive on this canvas, 2002 and 2003 none); tests/test_loss_plan_history.py pins it.
@@ -54,7 +74,18 @@ GUARD_ROWS = [(6000.0, "half range", dict(math=None, act_scale=4.0)), (40000.0, 
 
 
 def case_of(seq):
-    return WO.CASES[SEQUENCES[seq]["case"]]
+    case = SEQUENCES[seq]["case"]
+    return case if isinstance(case, dict) else WO.CASES[case]
+
+
+def extra_of(seq):
+    return dict(SEQUENCES[seq].get("extra", {}))
+
+
+def levels_of(seq):
+    """The flags of compute_losses a sequence's model takes, shallowest first, down to the sequence's deepest."""
+    ladder = [f for f, _ in (LEVELS if WO.is_dla(cpu_model(seq)) else V99_LEVELS)]
+    return ladder[:ladder.index(SEQUENCES[seq]["deepest"]) + 1]
 
 
 def _gt(model, inputs, seed, n_per_image, empty):
@@ -93,8 +124,15 @@ def guard_batch(model):
 
 
 @functools.lru_cache(maxsize=None)
+def _case_model(exp, weights):
+    return WO.case_model(dict(exp=exp, weights=weights, overrides=None))
+
+
 def cpu_model(seq):
-    return WO.case_model(case_of(seq))
+    """The sequence's CPU model with its synthetic weights; sequences of one configuration share it."""
+    case = case_of(seq)
+    assert case["overrides"] is None
+    return _case_model(case["exp"], case["weights"])
 
 
 def level_hw(model, inputs):

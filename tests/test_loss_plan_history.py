@@ -56,7 +56,7 @@ def test_consecutive_batches_differ_where_a_replayed_plan_could_keep_something(s
     assert smaller >= 1 or seq == "kitti_v99"  # stage_inputs leaves old pixels in the padding (one image per batch: nothing to pad)
 
 
-@pytest.mark.parametrize("seq", list(HC.SEQUENCES))
+@pytest.mark.parametrize("seq", [s for s, v in HC.SEQUENCES.items() if "case" in v["batches"].values()])
 def test_a_reused_pinned_seed_is_the_whole_model_cases_batch_unchanged(seq):
     case, model = HC.case_of(seq), HC.cpu_model(seq)
     inputs, gt = WO.case_inputs(case, model)
@@ -96,3 +96,32 @@ def test_levels_name_every_flag_of_compute_losses_in_order():
     assert flags == [f for f, _ in HC.LEVELS[1:]]
     known = set(inspect.signature(DD3D.get_loss_plan).parameters)
     assert all(p in known for _, p in HC.LEVELS[1:])
+    # the V2-99 ladder: the shared levels up to the FPN, then the two flags compute_losses takes from **branch
+    assert HC.V99_LEVELS[:5] == HC.LEVELS[:5] and [f for f, _ in HC.V99_LEVELS[5:]] == ["vovnet_grads", "vovnet_stem_grads"]
+    assert "vovnet_grads" in known and "vovnet_stem_grads" in known and "batch_stats" in known
+    assert all(HC.PLAN_FLAG[f] == p for f, p in HC.LEVELS + HC.V99_LEVELS)
+
+
+def test_the_new_sequences_are_what_the_gpu_tests_take_them_for():
+    """The batch-statistics sequences are the DLA sequences batch for batch; the two-image V2-99 sequences share their batches, have GT
+    in both images of A and in image 0 of B alone, and their smaller image is no multiple of any stride."""
+    S = HC.SEQUENCES
+    for seq in ("kitti_dla34", "nusc_dla34"):
+        twin = S[seq + "_bn"]
+        assert twin["extra"] == dict(batch_stats=True) and "extra" not in S[seq]
+        assert all(twin[k] is S[seq][k] for k in ("case", "deepest", "steps", "batches"))
+    a, b = S["kitti_v99_b2"], S["kitti_v99_b2_bn"]
+    assert b["extra"] == dict(batch_stats=True) and "extra" not in a and all(b["batches"][k] is a["batches"][k] for k in b["batches"])
+    assert a["steps"] == ["A", "B", "C", "A"] and b["steps"] == ["A", "B", "A"] and a["deepest"] == b["deepest"] == "vovnet_stem_grads"
+    case = HC.case_of("kitti_v99_b2")
+    assert (case["exp"], case["B"], case["H"], case["W"]) == ("dd3d_kitti_v99", 2, 128, 256)
+    model = HC.cpu_model("kitti_v99_b2")
+    counts = {k: [len(x["instances"].gt_classes) for x in HC.batch("kitti_v99_b2", k, model)] for k in "ABC"}
+    assert counts == {"A": [24, 24], "B": [24, 0], "C": [0, 0]}
+    h, w = a["batches"]["B"]["sizes"][1]
+    strides = [s.stride for s in model.backbone_output_shape]
+    assert all(h % s and w % s for s in [2] + strides) and h < case["H"] and w < case["W"]
+    assert HC.levels_of("kitti_v99_b2") == [f for f, _ in HC.V99_LEVELS] and HC.levels_of("kitti_dla34_bn") == [f for f, _ in HC.LEVELS]
+    for seq in ("kitti_dla34_bn", "nusc_dla34_bn", "kitti_v99_b2_bn"):  # the plan will have batch-statistics layers to run
+        from tests import tower_bn_oracle as TB
+        assert len(TB.bn_prefixes(HC.cpu_model(seq))) > 0

@@ -4,9 +4,13 @@ captured plan on other images and other GT every step.  The reference of a batch
 the same state dict, arithmetic and plane scale, hence a new plan with newly allocated, zero-filled buffers -- and the bar is bit
 equality everywhere: the kernels promise a fixed summation order and no float atomics.
 
-  1. sequences on one plan, at every flag level and on the other arithmetics;
-  2. other plans of the same model (inference on two canvases, a shallower loss plan) in between, with and without an eviction;
-  3. every floating-point tensor the backward's ops write overwritten with the seam tests' sentinel between two runs;
+  1. sequences on one plan, at every flag level and on the other arithmetics: DLA-34 on KITTI and nuScenes, on running statistics and with
+     batch_stats (tower_batch_stats() after every step, the model's own buffers at the end), V2-99 on one image down to the FPN and on
+     two images down to stem_1, with and without batch_stats;
+  2. other plans of the same model (inference on two canvases, a shallower loss plan, the running-statistics twin of a batch-statistics
+     plan) in between, with and without an eviction;
+  3. every floating-point tensor the backward's ops write -- under batch_stats also the statistics tensors and the scratch rows the
+     forward's reduction shares with the norm's backward -- overwritten with the seam tests' sentinel between two runs;
   4. the range guard's retry loop inside compute_losses, and plane scale 4 -- which only the guard reaches -- against the whole-model
      oracle of tests/test_whole_model_grads_gpu.py.
 """
@@ -24,7 +28,7 @@ from tests.util import scaled_between
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -12345.0  # the seam tests' (tests/test_predictor_grads_gpu.py, test_backbone_grads_gpu.py, test_stem_grads_gpu.py)
-_REFS = {}
+_REFS, _REF_STATS = {}, {}
 
 
 @pytest.fixture(autouse=True)
@@ -56,14 +60,39 @@ def _split(res):
 
 
 def _reference(seq, label, math=None, act_scale=None):
-    """(losses, grads, param_grads) of a fresh model on batch `label` alone at the sequence's deepest flag, once per configuration."""
+    """(losses, grads, param_grads) of a fresh model on batch `label` alone at the sequence's deepest flag and with its `extra`, once per
+    configuration; with batch_stats the fresh plan's tower_batch_stats() is kept beside them (_reference_stats)."""
     key = (seq, label, math, act_scale)
     if key not in _REFS:
         model = _fresh(seq, math, act_scale)
-        _REFS[key] = _split(model.compute_losses(_batch(seq, label), **{HC.SEQUENCES[seq]["deepest"]: True}))
+        extra = HC.extra_of(seq)
+        _REFS[key] = _split(model.compute_losses(_batch(seq, label), **{HC.SEQUENCES[seq]["deepest"]: True}, **extra))
+        if extra.get("batch_stats"):
+            _REF_STATS[key] = _plan(model, seq, HC.SEQUENCES[seq]["deepest"]).tower_batch_stats()
         torch.cuda.synchronize()
         del model
     return _REFS[key]
+
+
+def _reference_stats(seq, label, math=None, act_scale=None):
+    _reference(seq, label, math, act_scale)
+    return _REF_STATS[(seq, label, math, act_scale)]
+
+
+def _assert_stats_are(plan, seq, label, what, math=None, act_scale=None):
+    """plan.tower_batch_stats() after a step against the fresh plan's: every key of tower_bn_oracle.batch_stats_names, bit for bit."""
+    from tests import tower_bn_oracle as TB
+    got, want = plan.tower_batch_stats(), _reference_stats(seq, label, math, act_scale)
+    assert sorted(got) == sorted(want) == TB.batch_stats_names(HC.cpu_model(seq)) and len(got) > 0, (what, len(got), len(want))
+    bad = [(k, float((got[k].double() - want[k].double()).abs().max())) for k in got if not torch.equal(got[k], want[k])]
+    assert not bad, (what, f"{len(bad)} of {len(got)} statistics differ", " ".join(f"{k}:{d:.1e}" for k, d in bad[:24]))
+
+
+def _assert_buffers_kept(model, seq, what):
+    """The docstring of compute_losses: the model's own running statistics are never written."""
+    sd, loaded = model.state_dict(), HC.cpu_model(seq).state_dict()
+    keys = [k for k in sd if k.endswith("running_mean") or k.endswith("running_var")]
+    assert keys and all(torch.equal(sd[k].cpu(), loaded[k]) for k in keys), what
 
 
 def _assert_is(res, ref, what):
@@ -77,29 +106,35 @@ def _assert_is(res, ref, what):
         assert not bad, (what, part, f"{len(bad)} of {len(got)} entries differ", " ".join(f"{k}:{d:.1e}" for k, d in bad[:48]))
 
 
-def _flags(level):
-    return {level: True} if level else {}
+def _flags(level, seq=None):
+    return dict({level: True} if level else {}, **(HC.extra_of(seq) if seq else {}))
 
 
 def _plan(model, seq, level):
-    return model.get_loss_plan(*model.canvas_size(_batch(seq, HC.SEQUENCES[seq]["steps"][0])), **({HC.PLAN_FLAG[level]: True} if level else {}))
+    return model.get_loss_plan(*model.canvas_size(_batch(seq, HC.SEQUENCES[seq]["steps"][0])), **({HC.PLAN_FLAG[level]: True} if level else {}),
+                               **HC.extra_of(seq))
 
 
 def _run_sequence(seq, level, math=None, act_scale=None, use_graph=True):
     spec = HC.SEQUENCES[seq]
     model = _fresh(seq, math, act_scale, use_graph)
     plan = _plan(model, seq, level)  # built here; every step below must find it
-    first = None
+    first, bs = None, bool(HC.extra_of(seq).get("batch_stats"))
+    assert plan.batch_stats == bs and bool(plan.tower_bn) == bs
     for i, label in enumerate(spec["steps"]):
-        res = model.compute_losses(_batch(seq, label), **_flags(level))
+        res = model.compute_losses(_batch(seq, label), **_flags(level, seq))
         assert (isinstance(res, dict) if level is None else len(res) == (2 if level == "head_grads" else 3)), (seq, level, type(res))
         _assert_is(res, _reference(seq, label, math, act_scale), (seq, level, i, label))
         if level == spec["deepest"]:
             assert all(set(a) == set(b) for a, b in zip(_split(res), _reference(seq, label, math, act_scale)))
         first = first or res
         assert _plan(model, seq, level) is plan and len(model._plans) == 1, (seq, level, i)  # one plan throughout, no rebuild
+        if bs:
+            _assert_stats_are(plan, seq, label, (seq, level, i, label), math, act_scale)
     # what the first step returned was never cloned here: the values are copies, not views of plan buffers four batches later
     _assert_is(first, _reference(seq, spec["steps"][0], math, act_scale), (seq, level, "the first step's tensors after the last step"))
+    if bs:
+        _assert_buffers_kept(model, seq, (seq, level))
     return plan
 
 
@@ -166,6 +201,72 @@ def test_v99_sequence_on_one_plan(hiplib):
     _run_sequence("kitti_v99", "fpn_grads")
 
 
+@pytest.mark.parametrize("level", [f for f, _ in HC.V99_LEVELS], ids=lambda f: f or "losses")
+def test_two_image_v99_sequence_on_one_plan_at_every_flag_level(hiplib, level):
+    """V2-99 with a second image to pad (A, B, C, A; B's second image is 101 x 189, C has no GT): the eSE gate's per-image mean and the
+    ceil_mode pool read every pixel of the padded canvas, the VoVNet backward reads what they stored."""
+    plan = _run_sequence("kitti_v99_b2", level)
+    assert plan.B == 2 and (plan.Hp, plan.Wp) == (128, 256) and level in HC.levels_of("kitti_v99_b2")
+    assert hasattr(plan, "vovnet_layers") == (level in ("vovnet_grads", "vovnet_stem_grads"))
+    assert hasattr(plan, "vovnet_stem_layers") == (level == "vovnet_stem_grads")
+
+
+@pytest.mark.parametrize("how", ["bf16x3", "launch_by_launch"])
+def test_two_image_v99_sequence_on_one_plan_other_arithmetic_and_no_graph(hiplib, how):
+    from dd3d_amd import hip
+    kw = dict(bf16x3=dict(math="bf16x3"), launch_by_launch=dict(use_graph=False))[how]
+    plan = _run_sequence("kitti_v99_b2", "vovnet_stem_grads", **kw)
+    assert (plan.math == hip.MATH_BF16X3) == (how == "bf16x3") and (plan.graph is None) == (how == "launch_by_launch")
+
+
+@pytest.mark.parametrize("level", ["tower_grads", "fpn_grads", "stem_grads"])
+def test_kitti_batch_statistics_sequence_on_one_plan(hiplib, level):
+    """kitti_dla34's five steps with the towers' BatchNorm on the batch's statistics: they sum over the whole padded canvas, so a stale
+    pixel in the padding of B and D or a stale row of the shared scratch moves every tower output.  tower_batch_stats() is compared
+    after every step, the model's own running statistics after the last."""
+    plan = _run_sequence("kitti_dla34_bn", level)
+    assert len(plan.tower_bn) == 8 and plan.bn_part is not None
+
+
+@pytest.mark.parametrize("how", ["bf16x3", "plane_scale_1", "launch_by_launch"])
+def test_kitti_batch_statistics_sequence_on_one_plan_other_arithmetics_and_no_graph(hiplib, how):
+    from dd3d_amd import hip
+    kw = dict(bf16x3=dict(math="bf16x3"), plane_scale_1=dict(act_scale=1.0), launch_by_launch=dict(use_graph=False))[how]
+    plan = _run_sequence("kitti_dla34_bn", "stem_grads", **kw)
+    buf = plan.bufs["level5.cat"]
+    if how == "bf16x3":
+        assert plan.math == hip.MATH_BF16X3 and buf.np == 3 and not buf.f16
+    else:
+        assert buf.f16 and buf.plane_scale == (1.0 if how == "plane_scale_1" else 16.0)
+    assert (plan.graph is None) == (how == "launch_by_launch")
+
+
+def test_nuscenes_batch_statistics_sequence_on_one_plan(hiplib):
+    plan = _run_sequence("nusc_dla34_bn", "stem_grads")
+    assert plan.nusc and plan.B == 6 and plan.batch_stats
+
+
+def test_two_image_v99_batch_statistics_sequence_on_one_plan(hiplib):
+    plan = _run_sequence("kitti_v99_b2_bn", "vovnet_stem_grads")
+    assert plan.batch_stats and plan.with_vovnet_stem_grads and plan.B == 2
+
+
+def test_forty_replays_of_the_v99_batch_statistics_plan_keep_their_bits(hiplib):
+    """The forty-replay test's argument on a graph several times longer: the V2-99 backward down to stem_1 behind batch-statistics
+    towers.  Every replay equals the fresh reference, the statistics included, and the renormalisation trigger word stays 0."""
+    seq = "kitti_v99_b2_bn"
+    model = _fresh(seq)
+    ref = _reference(seq, "A")
+    for i in range(40):
+        res = model.compute_losses(_batch(seq, "A"), vovnet_stem_grads=True, batch_stats=True)
+        plan = _plan(model, seq, "vovnet_stem_grads")
+        assert int(plan.targets.flags[0]) == 0, (i, hex(int(plan.targets.flags[0]) & 0xFFFFFFFF))
+        _assert_is(res, ref, (seq, "replay", i))
+        _assert_stats_are(plan, seq, "A", (seq, "replay", i))
+    assert len(model._plans) == 1
+    _assert_buffers_kept(model, seq, seq)
+
+
 # ------------------------------------------------------------------------------------------------------ 2. other plans in between
 @pytest.mark.parametrize("max_cached_plans", [None, 2], ids=["cached", "evicted"])
 def test_other_plans_of_the_model_run_in_between(hiplib, max_cached_plans):
@@ -194,6 +295,56 @@ def test_other_plans_of_the_model_run_in_between(hiplib, max_cached_plans):
         assert plans[1] is not plans[0] and plans[2] is not plans[1] and len(model._plans) == 2  # rebuilt: new buffers, the same bits
 
 
+def _detections(out):
+    """An inference result as plain CPU tensors per image."""
+    rows = []
+    for o in out:
+        i = o["instances"]
+        rows.append([t.detach().cpu().clone() for t in (i.pred_boxes.tensor, i.scores, i.scores_3d, i.pred_classes, i.pred_boxes3d.vectorize())])
+    return rows
+
+
+def _inference_reference(seq, label):
+    key = (seq, label, "inference")
+    if key not in _REFS:
+        model = _fresh(seq)
+        _REFS[key] = _detections(model(_batch(seq, label)))
+        torch.cuda.synchronize()
+        del model
+    return _REFS[key]
+
+
+@pytest.mark.parametrize("max_cached_plans", [None, 2], ids=["cached", "evicted"])
+def test_batch_and_running_statistics_forwards_share_one_weight_store(hiplib, max_cached_plans):
+    """A, B, A on ONE model: compute_losses(stem_grads, batch_stats), compute_losses(stem_grads) on the running statistics, an inference.
+    The batch-statistics towers run the model's packed filters through a raw epilogue with scale ones, the other two through the
+    folded norm; the `descaled` vectors and the term planes live in the model's shared weight store.  Each result equals its own
+    fresh reference.  With a cache of two plans each of the three is rebuilt in every round: new buffers, the same bits."""
+    seq, bn = "kitti_dla34", "kitti_dla34_bn"
+    model = _fresh(seq)
+    if max_cached_plans is not None:
+        model.max_cached_plans = max_cached_plans
+    plans = []
+    for i, label in enumerate(["A", "B", "A"]):
+        res = model.compute_losses(_batch(seq, label), stem_grads=True, batch_stats=True)
+        _assert_is(res, _reference(bn, label), (bn, max_cached_plans, i, label))
+        plan = _plan(model, bn, "stem_grads")  # (a cache hit: the plan that just ran)
+        _assert_stats_are(plan, bn, label, (bn, max_cached_plans, i, label))
+        res = model.compute_losses(_batch(seq, label), stem_grads=True)
+        _assert_is(res, _reference(seq, label), (seq, max_cached_plans, i, label))
+        other = _plan(model, seq, "stem_grads")
+        assert other is not plan and not other.batch_stats and plan.batch_stats
+        got, want = _detections(model(_batch(seq, label))), _inference_reference(seq, label)
+        assert len(got) == len(want) == 2 and all(len(g[1]) > 0 for g in want)
+        assert all(torch.equal(a, b) for g, w in zip(got, want) for a, b in zip(g, w)), (seq, max_cached_plans, i, label, "inference")
+        plans.append((plan, other))
+    if max_cached_plans is None:
+        assert all(p is plans[0][0] and o is plans[0][1] for p, o in plans) and len(model._plans) == 3
+    else:
+        assert plans[1][0] is not plans[0][0] and plans[2][0] is not plans[1][0] and plans[1][1] is not plans[0][1] and len(model._plans) == 2
+    _assert_buffers_kept(model, bn, (bn, max_cached_plans))
+
+
 # ------------------------------------------------------------------------------------------------------------ 3. poisoned outputs
 # Floating-point tensors on the backward side that NO kernel writes: build-time constants the ops only read.  Nothing here may be
 # written by any op; the test asserts that a run leaves every one of them unchanged.  (name pattern, reason)
@@ -201,18 +352,31 @@ EXCLUDED = [
     ("upstream", "the vector of ones dd3d_loss_backward reads as the gradient of the sum of the loss dict; filled once when the plan is built"),
     ("fpn_layers.*.g[*]", "the zero gradient standing in for an FPN output that DD3D.IN_FEATURES does not select: torch.zeros when the plan is "
                           "built, read by the FPN backward, written by nothing (the released configs select every output)"),
+    ("tower_ones[*]", "the all-ones f32 tensor per level that the batch-statistics layers' two GEMMs read as the stored output whose sign "
+                      "masks the gradient (the norm's backward has applied the real mask already); torch.ones when the plan is built"),
 ]
+NEW_CALLS = ("EseGrads", "Pool3Grads", "SumGrads", "VovnetConvGrads", "VovnetStemGrads")  # what the VoVNet stages contribute
 
 
 def _backward_outputs(plan):
-    """({name: tensor} of every floating-point tensor an op of the plan writes on the backward side, {name: tensor} of the constants)."""
+    """({name: tensor} of every floating-point tensor an op of the plan writes on the backward side -- and, under batch statistics, the
+    forward-side tensors that are no named buffers: every tower layer's statistics and the scratch rows they share with the norm's
+    backward --, {name: tensor} of the constants)."""
     out = {}
-    groups = [("pred_groups", plan.pred_groups), ("tower_layers", plan.tower_layers), ("fpn_layers", plan.fpn_layers),
-              ("backbone_layers", plan.backbone_layers), ("stem_layers", plan.stem_layers)]
+    groups = [(g, getattr(plan, g)) for g in ("pred_groups", "tower_layers", "fpn_layers")]
+    groups += [(g, getattr(plan, g, {})) for g in ("backbone_layers", "stem_layers", "vovnet_layers", "vovnet_stem_layers")]  # by backbone and depth
     for gname, group in groups:
         for key, lay in group.items():
             for j, (t, _) in enumerate(lay._raw):
                 out[f"{gname}.{key}.raw{j}"] = t
+    for key, lay in plan.tower_layers.items():  # the norm's backward of a batch-statistics layer: qp and gc
+        for j, (t, _) in enumerate(lay.bn._raw if lay.bn is not None else ()):
+            out[f"tower_layers.{key}.bn.raw{j}"] = t
+    for (_, i), rec in plan.tower_bn.items():  # one statistics tensor per tower depth, shared by its towers
+        if all(rec["stats"].data_ptr() != t.data_ptr() for t in out.values()):
+            out[f"tower_bn.{i}.stats"] = rec["stats"]
+    if plan.tower_bn:
+        out["bn_part"] = plan.bn_part
     out["tower_slab.part"], out["tower_slab.qpart"] = plan.tower_slab
     for name, maps in (("d_cls", plan.d_cls), ("d_b2d", plan.d_b2d), ("d_b3d", plan.d_b3d or [])):
         for l, t in enumerate(maps):
@@ -226,33 +390,87 @@ def _backward_outputs(plan):
         for l, g in enumerate(lay.keep[0]):
             if not owned(g):
                 const[f"fpn_layers.{key}.g[{l}]"] = g
+    for l, t in enumerate(plan.tower_ones or ()):
+        const[f"tower_ones[{l}]"] = t
+    assert not any(owned(t) for t in const.values())
     return out, const
 
 
-@pytest.mark.parametrize("seq", ["kitti_dla34", "nusc_dla34"])
+def _grad_calls_in_the_ops(plan):
+    """Every GradCall a launch of the plan is bound to, found by walking plan.ops -- not through the plan's layer dicts."""
+    from dd3d_amd.engine.losses import GradCall
+    calls = []
+    for op in plan.ops:
+        fn = getattr(op, "fn", None)
+        bound = list(getattr(fn, "__defaults__", None) or ()) + [c.cell_contents for c in getattr(fn, "__closure__", None) or ()]
+        calls += [b for b in bound if isinstance(b, GradCall) and all(b is not c for c in calls)]
+    return calls
+
+
+def _assert_structural_coverage(plan, outputs, seq):
+    """The poisoned tensors are every `_raw` tensor of every gradient call among the plan's launches, whatever stage it belongs to; the
+    VoVNet stages and the batch-statistics norms contributed."""
+    calls = _grad_calls_in_the_ops(plan)
+    want = {(t.data_ptr(), t.numel()) for c in calls for t, _ in c._raw}
+    got = {(t.data_ptr(), t.numel()) for n, t in outputs.items() if ".raw" in n}
+    assert got == want and len(want) > 100, (seq, len(got), len(want), len(got ^ want))
+    kinds = {type(c).__name__ for c in calls}
+    if hasattr(plan, "vovnet_stem_layers"):
+        assert set(NEW_CALLS) <= kinds, (seq, sorted(kinds))
+        by_group = {type(lay).__name__ for g in ("vovnet_layers", "vovnet_stem_layers") for lay in getattr(plan, g).values()}
+        assert by_group == set(NEW_CALLS), (seq, sorted(by_group))
+    spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in outputs.values()]
+    owned = lambda t: any(a <= t.data_ptr() and t.data_ptr() + t.numel() * t.element_size() <= b for a, b in spans)
+    if plan.batch_stats:
+        assert "TowerBnGrads" in kinds and len(plan.tower_bn) > 0 and owned(plan.bn_part)
+        for key, rec in plan.tower_bn.items():
+            bn = plan.tower_layers[key].bn
+            assert owned(bn.qp) and all(owned(g) for g in bn.gc) and owned(rec["stats"]), (seq, key)
+    else:
+        assert not plan.tower_bn and plan.tower_ones is None
+
+
+POISON = ["kitti_dla34", "nusc_dla34", "kitti_dla34_bn", "kitti_v99_b2", "kitti_v99_b2_bn"]
+
+
+@pytest.mark.parametrize("seq", POISON)
 def test_poisoned_backward_outputs_change_no_bit(hiplib, seq):
     """Step A, then every tensor the backward's ops write holds the sentinel, then step A again: the same bits.  A kernel that skips a
-    store it owes -- an all-zero block, a slice whose units were all skipped -- would hand the sentinel on.  Integer and index tensors,
-    the forward's activations, the staged inputs and the parameter-derived constants are not touched (the sequences cover them)."""
+    store it owes -- an all-zero block, a slice whose units were all skipped -- would hand the sentinel on.  Under batch statistics the
+    statistics tensors and the scratch rows of the forward's reduction are written too and hold the sentinel as well.  Integer and index
+    tensors, the forward's named activation buffers (towerraw* among them), the staged inputs and the parameter-derived constants are
+    not touched (the sequences cover them)."""
+    level, flags = HC.SEQUENCES[seq]["deepest"], _flags(HC.SEQUENCES[seq]["deepest"], seq)
+    bs = bool(flags.get("batch_stats"))
     model = _fresh(seq)
     batch = _batch(seq, "A")
-    first = _split(model.compute_losses(batch, stem_grads=True))
+    first = _split(model.compute_losses(batch, **flags))
     _assert_is(first, _reference(seq, "A"), (seq, "before"))
-    plan = _plan(model, seq, "stem_grads")
+    plan = _plan(model, seq, level)
     outputs, const = _backward_outputs(plan)
     matches = lambda name: any(fnmatch.fnmatchcase(name, pat.replace("[", "[[]")) for pat, _ in EXCLUDED)
     assert all(matches(n) for n in const) and not any(matches(n) for n in outputs)
-    assert len(outputs) > 200 and sum(t.numel() for t in outputs.values()) > 5_000_000
+    if seq in ("kitti_dla34", "nusc_dla34"):
+        assert len(outputs) > 200 and sum(t.numel() for t in outputs.values()) > 5_000_000
+    _assert_structural_coverage(plan, outputs, seq)
+    assert bs == any(n.startswith("tower_ones") for n in const)
+    print(f"[loss_plan_history] poisoned {seq}: {len(outputs)} tensors, {sum(t.numel() for t in outputs.values())} words, {len(const)} constants")
     torch.cuda.synchronize()
     before = {n: t.clone() for n, t in const.items()}
+    stats = plan.tower_batch_stats() if bs else {}
     for t in outputs.values():
         t.fill_(SENTINEL)
-    second = _split(model.compute_losses(batch, stem_grads=True))
-    assert _plan(model, seq, "stem_grads") is plan
+    second = _split(model.compute_losses(batch, **flags))
+    assert _plan(model, seq, level) is plan
     _assert_is(second, first, (seq, "after the sentinel"))
     assert all(set(a) == set(b) for a, b in zip(second, first))
     assert all(torch.equal(const[n], before[n]) for n in const)  # no op writes what the list excludes
     assert not any(bool((v == SENTINEL).any()) for d in second for v in d.values())
+    if bs:
+        after = plan.tower_batch_stats()
+        assert sorted(after) == sorted(stats) and all(torch.equal(after[k], stats[k]) for k in stats)
+        assert not any(bool((v == SENTINEL).any()) for v in after.values())
+        _assert_stats_are(plan, seq, "A", (seq, "after the sentinel"))
 
 
 # ------------------------------------------------------------------------------------- 4. the guard's retry loop in compute_losses

@@ -28,16 +28,19 @@ class Reference:
         self.model = WO.case_model(self.case)
         self.inputs, self.gt = WO.case_inputs(self.case, self.model)
         self.extras = {}
-        self.params, self.at, self.pre = WO.whole_model_grads(self.model, self.model.cfg, self.inputs, self.gt, F64, extras=self.extras)
+        self.batch_stats = bool(self.case.get("batch_stats"))
+        self.params, self.at, self.pre = WO.whole_model_grads(self.model, self.model.cfg, self.inputs, self.gt, F64, extras=self.extras,
+                                                              batch_stats=self.batch_stats)
 
     @functools.cached_property
     def pre32(self):
-        return WO.whole_model_grads(self.model, self.model.cfg, self.inputs, self.gt, torch.float32)[2]
+        return WO.whole_model_grads(self.model, self.model.cfg, self.inputs, self.gt, torch.float32, batch_stats=self.batch_stats)[2]
 
     @functools.cached_property
     def sites(self):
         from dd3d_amd.engine.losses import LossPlan
-        return WO.relu_sites(LossPlan(self.model, *self.model.canvas_size(self.inputs), device="cpu", dry_run=True, **{self.case["grads"]: True}))
+        return WO.relu_sites(LossPlan(self.model, *self.model.canvas_size(self.inputs), device="cpu", dry_run=True, batch_stats=self.batch_stats,
+                                      **{self.case["grads"]: True}))
 
 
 @functools.lru_cache(maxsize=None)
@@ -105,6 +108,39 @@ def test_a_forced_mask_is_honoured():
     assert not torch.equal(w[ch], w0[ch]) and torch.equal(w[rest], w0[rest])
     assert not torch.equal(params["backbone.bottom_up.level2.tree1.conv1.weight"], ref.params["backbone.bottom_up.level2.tree1.conv1.weight"])  # everything upstream moves
     assert torch.equal(params["backbone.bottom_up.level5.root.conv.weight"], ref.params["backbone.bottom_up.level5.root.conv.weight"])  # nothing downstream does
+
+
+def test_batch_statistics_switch_is_the_train_mode_tower_forward_and_its_autograd():
+    """whole_model_grads(batch_stats=True) -- the batch_norm method of the intercepting functional -- against tower_bn_oracle's own
+    switch, which replaces the oracle's norm function: the head maps on the pass' own FPN features are tower_bn_oracle.head_maps, and
+    the gradients are plain autograd of the whole forward under that other switch.  Every norm of the two BN towers takes the
+    batch's statistics (four layers, one norm per level: the call count is checked against bn_prefixes), the state dict's running
+    statistics stay, and the running-statistics forward is another function."""
+    from tests import tower_bn_oracle as TB
+    ref, base = reference("kitti_dla34_batch_stats"), reference("kitti_dla34")
+    assert ref.batch_stats and not base.batch_stats and ref.case["gt_seed"] == base.case["gt_seed"]
+    model, ex = ref.model, ref.extras
+    prefixes = TB.bn_prefixes(model)
+    L = ex["p"]["num_levels"]
+    assert len(prefixes) == 8 * L  # cls and box2d towers, four layers each, one norm per level
+    sd0 = {k: v.clone() for k, v in model.state_dict().items()}
+    with torch.no_grad():
+        maps = TB.head_maps(model, ex["features"], F64)
+    assert sorted(maps) == sorted(ex["maps"]) and all(torch.equal(maps[k], ex["maps"][k]) for k in maps)
+    assert not torch.equal(ex["maps"]["logits0"], base.extras["maps"]["logits0"]) and all(torch.equal(a, b) for a, b in zip(ex["features"], base.extras["features"]))
+    with TB.batch_statistics(prefixes):
+        params, at, pre = WO.whole_model_grads(model, model.cfg, ref.inputs, ref.gt, F64)
+    assert sorted(params) == sorted(ref.params) and sorted(at) == sorted(ref.at) and len(pre) == len(ref.pre)
+    assert all(torch.equal(params[k], ref.params[k]) for k in params) and all(torch.equal(at[k], ref.at[k]) for k in at)
+    assert all(torch.equal(a, b) for a, b in zip(pre, ref.pre))
+    moved = {k for k in params if not torch.equal(ref.params[k], base.params[k])}  # (the FrozenBN box3d tower and its predictors stay)
+    cls = [p for p in prefixes if "cls_tower" in p]  # the classification loss reaches every location of every level
+    assert len(cls) == 4 * L and all(p + ".weight" in moved and p + ".bias" in moved for p in cls)
+    assert any("box2d_tower" in k for k in moved) and "backbone.bottom_up.level2.tree1.conv1.weight" in moved
+    assert all(torch.equal(v, sd0[k]) for k, v in model.state_dict().items())  # the statistics in the state dict are never written
+    with pytest.raises(ValueError, match="batch-statistics norm calls"):  # a switch that reaches no norm is an error, not a silent eval forward
+        with TB.batch_statistics(prefixes):
+            WO.whole_model_grads(model, model.cfg, ref.inputs, ref.gt, F64, backward=False, batch_stats=True)
 
 
 # ------------------------------------------------------------------------------------------------------------ the stages compose

@@ -1,5 +1,6 @@
 """The composed training backward on the MI355X against ONE autograd pass of the whole model (tests/whole_model_grad_oracle.py):
-param_grads and grads of DD3D.compute_losses(inputs, backbone_grads=True) (V2-99: fpn_grads=True) are the gradient of the sum of the loss
+param_grads and grads of DD3D.compute_losses(inputs, backbone_grads=True) (V2-99: fpn_grads=True; one case with batch_stats=True, the
+oracle's tower norms then on the batch's statistics as well) are the gradient of the sum of the loss
 dict with respect to the model's parameters, the stem's output, the backbone's output features, the FPN outputs and the head maps.
 
 The five stage tests feed each stage's oracle the gradient the previous stage's kernels produced; nothing here comes from the kernels but
@@ -30,7 +31,7 @@ def _natural_forward(case, cpu, inputs, gt, inv_K):
     key = case["ref"]
     if key not in _NATURAL:
         ex = {}
-        pre = WO.whole_model_grads(cpu, cpu.cfg, inputs, gt, F64, inv_K=inv_K, extras=ex, backward=False)[2]
+        pre = WO.whole_model_grads(cpu, cpu.cfg, inputs, gt, F64, inv_K=inv_K, extras=ex, backward=False, batch_stats=bool(case.get("batch_stats")))[2]
         _NATURAL[key] = (pre, ex, inv_K.clone())
     pre, ex, k0 = _NATURAL[key]
     assert torch.equal(k0, inv_K)
@@ -61,6 +62,9 @@ def compare_with_whole_model_oracle(name, case, model, cpu, inputs, gt):
     Returns (the worst use of the factor 8, losses, grads, param_grads of the call)."""
     from tests.test_losses_gpu import _close
     through = {case["grads"]: True}  # backbone_grads, or fpn_grads for V2-99, whose backward stops at the backbone's output features
+    bs = bool(case.get("batch_stats"))  # the towers' BatchNorm on the batch's statistics, in the plan and in the oracle alike
+    if bs:
+        through["batch_stats"] = True
     losses, grads, params = model.compute_losses(inputs, **through)
     plan = model.get_loss_plan(*model.canvas_size(inputs), **through)
     if case["math"] == "bf16x3":  # the case's arithmetic and plane scale reached the stored activations
@@ -83,8 +87,8 @@ def compare_with_whole_model_oracle(name, case, model, cpu, inputs, gt):
     assert far == 0 and bad <= WO.SIGN_CAP * total, (name, bad, far, total)
 
     e32 = {}
-    p64, a64, _ = WO.whole_model_grads(cpu, cpu.cfg, inputs, gt, F64, masks=masks, inv_K=inv_K)
-    p32, a32, _ = WO.whole_model_grads(cpu, cpu.cfg, inputs, gt, F32, masks=masks, inv_K=inv_K, extras=e32)
+    p64, a64, _ = WO.whole_model_grads(cpu, cpu.cfg, inputs, gt, F64, masks=masks, inv_K=inv_K, batch_stats=bs)
+    p32, a32, _ = WO.whole_model_grads(cpu, cpu.cfg, inputs, gt, F32, masks=masks, inv_K=inv_K, extras=e32, batch_stats=bs)
 
     # every returned parameter, by stage and family; the key sets match
     stage_of = lambda k: WO.stage_and_family(k, backbone_grads=case["grads"] == "backbone_grads")
@@ -124,7 +128,7 @@ def test_composed_backward_is_the_whole_model_gradient(hiplib, name):
     inputs, gt = WO.case_inputs(case, cpu)
     for x, g in zip(inputs, gt):
         x["instances"] = g
-    through = {case["grads"]: True}
+    through = dict({case["grads"]: True}, **({"batch_stats": True} if case.get("batch_stats") else {}))
     _, losses, grads, params = compare_with_whole_model_oracle(name, case, model, cpu, inputs, gt)
 
     # a second call is bit-equal; the captured graph equals launch-by-launch execution

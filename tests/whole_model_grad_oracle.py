@@ -47,12 +47,21 @@ class _MaskedRelu(torch.autograd.Function):
 
 class _Functional:
     """Stands for torch.nn.functional inside the oracle modules: every relu call is recorded (input and output, call order) and, with
-    `masks`, differentiated through masks[call index]."""
-    def __init__(self, masks):
+    `masks`, differentiated through masks[call index].  `batch_stats`: the weight leaves of the norms that normalise with the batch's
+    statistics, as nn.BatchNorm2d does in train() (the head towers' norms under compute_losses(batch_stats=True)); every other
+    batch_norm call goes through unchanged."""
+    def __init__(self, masks, batch_stats=()):
         self.masks, self.pre, self.out = masks, [], []
+        self.batch_stats, self.bn_calls = {id(w) for w in batch_stats}, 0
 
     def __getattr__(self, name):
         return getattr(F, name)
+
+    def batch_norm(self, x, running_mean, running_var, weight=None, bias=None, training=False, momentum=0.1, eps=1e-5):
+        if id(weight) not in self.batch_stats:
+            return F.batch_norm(x, running_mean, running_var, weight, bias, training=training, momentum=momentum, eps=eps)
+        self.bn_calls += 1  # (clones: train() would update the running statistics in place, the state dict keeps its own)
+        return F.batch_norm(x, running_mean.clone(), running_var.clone(), weight, bias, training=True, momentum=0.1, eps=eps)
 
     def relu(self, x, inplace=False):
         k = len(self.pre)
@@ -68,11 +77,11 @@ class _Functional:
 
 
 @contextlib.contextmanager
-def intercepted(masks=None):
-    """The oracle forward under observation: its ReLUs go through a _Functional; the FPN reads aliases of the backbone features and the
+def intercepted(masks=None, batch_stats=()):
+    """The oracle forward under observation: its ReLUs and batch norms go through a _Functional; the FPN reads aliases of the backbone features and the
     heads read aliases of the FPN outputs, so that the gradient AT an alias is the consumer's contribution alone (what the kernels'
     backbone_<name> and feature<l> are: the FPN's part without the next tree's, the towers' part without P6's)."""
-    fn = _Functional(masks)
+    fn = _Functional(masks, batch_stats)
     rec = {"F": fn, "bottom_up": None, "features": None, "cls_tower_out": None}
     saved = (O.F, NO.F, O.fpn_forward, O.dd3d_backbone, O.fcos2d_head, VO.F)
 
@@ -118,7 +127,7 @@ def free_relus(model):
     return 3 + sum(blocks) * (layers + 1)
 
 
-def whole_model_grads(model_cpu, cfg, inputs, gt, dtype, masks=None, inv_K=None, extras=None, backward=True):
+def whole_model_grads(model_cpu, cfg, inputs, gt, dtype, masks=None, inv_K=None, extras=None, backward=True, batch_stats=False):
     """d (sum of the loss dict) / d (every named parameter of `model_cpu`) by one autograd pass in `dtype`: the state-dict tensors are
     the leaves, the images are cast to `dtype`.  Returns
       ({parameter name: gradient},
@@ -127,7 +136,9 @@ def whole_model_grads(model_cpu, cfg, inputs, gt, dtype, masks=None, inv_K=None,
        [the ReLU pre-activations in call order, detached]).
     `masks`: one boolean tensor per ReLU call that replaces the derivative's own sign test.  `inv_K` (B, 3, 3): default, the float32
     inverse of the inputs' intrinsics.  `extras`: a dict that receives losses, maps, targets, p, inv_K, relu_out, features and bottom_up (detached).
-    `backward=False`: the forward alone (the pre-activations and the extras; both gradient dicts empty)."""
+    `backward=False`: the forward alone (the pre-activations and the extras; both gradient dicts empty).  `batch_stats`: the head towers'
+    trainable BatchNorm2d layers (tower_bn_oracle.bn_prefixes) normalise with the batch's statistics, per level, and the backward goes
+    through both statistics: the forward of the reference's train() in the towers, every other norm on its running statistics."""
     nusc = hasattr(model_cpu, "attr_logits")
     sd = {k: (v.detach().to(dtype).clone() if v.is_floating_point() else v.detach()) for k, v in model_cpu.state_dict().items()}
     names = [k for k, _ in model_cpu.named_parameters()]
@@ -136,13 +147,19 @@ def whole_model_grads(model_cpu, cfg, inputs, gt, dtype, masks=None, inv_K=None,
     batch = [dict(x, image=x["image"].to(dtype)) for x in inputs]
     if inv_K is None:
         inv_K = torch.linalg.inv(torch.stack([x["intrinsics"] for x in inputs]).float())
-    with intercepted(masks) as rec:
+    bn_leaves = []
+    if batch_stats:
+        from tests import tower_bn_oracle as TB
+        bn_leaves = [sd[p + ".weight"] for p in sorted(TB.bn_prefixes(model_cpu))]
+    with intercepted(masks, bn_leaves) as rec:
         _, st = O.dd3d_forward(sd, cfg, batch, stop_after_heads=True)
         keys = [k for k in GO.FAMILIES[:8] if k in st]
         if nusc:
             st["attr"], st["speed"] = NO.nuscenes_heads(sd, rec["cls_tower_out"])
             keys += ["attr", "speed"]
     fn = rec["F"]
+    if batch_stats and fn.bn_calls != len(bn_leaves):  # per-level norms: one call each
+        raise ValueError(f"{fn.bn_calls} batch-statistics norm calls for {len(bn_leaves)} tower norms")
     if masks is not None and len(masks) != len(fn.pre):
         raise ValueError(f"{len(masks)} masks for {len(fn.pre)} ReLU calls")
     L = len(st["logits"])
@@ -284,7 +301,7 @@ def tensor_family_of(key):
 BN_EVERYWHERE = {"FE": {"BACKBONE": {"NORM": "BN"}, "FPN": {"NORM": "BN"}}}  # the towers' norm is BN in the released configs
 _KITTI = dict(exp="dd3d_kitti_dla34", weights="dla34_kitti", overrides=None, B=2, H=128, W=384, ds="kitti", gt_seed=2004, n_per_image=24, positives=150, relus=99,
               grads="backbone_grads")
-# One entry per case of the GPU test.  `ref`: the cases that share a CPU reference (model, inputs, GT).  GT seeds: scanned on the CPU for
+# One entry per case of the GPU test.  `ref`: the cases that share a CPU reference (model, inputs, GT, batch_stats).  GT seeds: scanned on the CPU for
 # a batch with no positive inside loss_grad_oracle.KINK_MARGIN of a non-smooth point of the loss on the float64 oracle's head maps (one
 # such positive moves every parameter upstream of it by far more than rounding) -- tests/test_whole_model_grads.py pins seed, positive
 # count and the empty kink mask.  nuScenes: six boxes per image; with the default 24 every seed of 2000 .. 2011 has 2 to 13 kink positives.
@@ -299,6 +316,10 @@ CASES = {
     "kitti_v99": dict(exp="dd3d_kitti_v99", weights="v99_kitti", overrides=None, B=1, H=128, W=256, ds="kitti", gt_seed=2000, n_per_image=24, positives=170,
                       relus=164, grads="fpn_grads", ref="kitti_v99", math=None, act_scale=None),
 }
+# Batch statistics in the head towers (compute_losses(batch_stats=True)): the head maps change, so the seeds were scanned again on the
+# float64 train-mode forward (2000 .. 2015: 2002, 2004 and 2010 leave no positive inside the kink margin; 2004 keeps the batch of the
+# running-statistics cases).
+CASES["kitti_dla34_batch_stats"] = dict(_KITTI, ref="kitti_dla34_batch_stats", math=None, act_scale=None, batch_stats=True)
 REFERENCES = sorted({c["ref"] for c in CASES.values()})
 
 
