@@ -1,5 +1,6 @@
 """Dense-depth loss engine: the per-level training loss dict of DD3DDenseDepth on the MI355X and, on request, its gradient with respect to
-the head's per-level maps (backward through the convolutions is not implemented).
+the head's per-level maps and from there, stage by stage, with respect to every parameter of the network: the stages are LossPlan's
+(losses.BackwardStages: predictor group, tower, FPN, DLA-34 or VoVNet-V2 with their stems), appended behind the loss backward.
 
 ``DenseDepthLossPlan`` has the trunk, tower and predictors of ``DenseDepthPlan`` and, in place of the five up-sampling launches, ONE call of
 csrc/dense_depth_loss.hip: a single pass over the ground-truth canvas that evaluates every level's up-sampled prediction in place at the
@@ -13,6 +14,7 @@ import torch
 
 from dd3d_amd import hip
 from dd3d_amd.engine.forward import DenseDepthPlan
+from dd3d_amd.engine.losses import BackwardStages
 from dd3d_amd.engine.ops import CallOp
 from dd3d_amd.engine.plan import PlanBase
 
@@ -82,16 +84,27 @@ def stage_depth_canvas(canvas, depths, image_sizes, checked=False):
     return canvas
 
 
-class DenseDepthLossPlan(DenseDepthPlan):
+class DenseDepthLossPlan(BackwardStages, DenseDepthPlan):
     """Trunk, box3d tower and per-level predictors of DenseDepthPlan, then one dd3d_dense_depth_loss call on the raw predictor maps and the
     ground-truth canvas; captured as one hipGraph by DD3DDenseDepth.get_loss_plan.  `head_grads`: one dd3d_dense_depth_loss_backward call
-    more, in the same graph, into gradient buffers the plan owns (upstream = 1: the gradient of the sum of the dict's values)."""
-    def __init__(self, model, B, Hp, Wp, device=None, dry_run=False, head_grads=False):
+    more, in the same graph, into gradient buffers the plan owns (upstream = 1: the gradient of the sum of the dict's values).  The deeper
+    flags append LossPlan's backward stages behind it (losses.BackwardStages; each implies the shallower ones and refuses what LossPlan
+    refuses): `pred_grads` the one predictor group (n = 1 at pitch 4, a filter per level, Scale / Offset in slot 0), `tower_grads` the
+    box3d tower, `fpn_grads` the FPN, `backbone_grads` / `stem_grads` DLA-34, `vovnet_grads` / `vovnet_stem_grads` the VoVNet-V2
+    backbones; `batch_stats` normalises a trainable-BatchNorm2d tower with the batch's statistics, forward and backward.  From
+    `tower_grads` on every tower layer keeps its output (5 levels x NUM_CONVS buffers of 256 channels in place of the two ping / pong
+    sets); every other plan launches exactly what it launched before these flags existed."""
+    def __init__(self, model, B, Hp, Wp, device=None, dry_run=False, head_grads=False, pred_grads=False, tower_grads=False, fpn_grads=False,
+                 backbone_grads=False, stem_grads=False, vovnet_grads=False, vovnet_stem_grads=False, batch_stats=False):
+        self._chain_flags(model, B, Hp, Wp, grads=head_grads, pred_grads=pred_grads, tower_grads=tower_grads, fpn_grads=fpn_grads,
+                          backbone_grads=backbone_grads, stem_grads=stem_grads, vovnet_grads=vovnet_grads, batch_stats=batch_stats,
+                          vovnet_stem_grads=vovnet_stem_grads)
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
         weight, beta, min_depth, max_depth = dense_depth_loss_config(model.cfg)  # (read here, not in the model's constructor)
         self.adopt_weight_store(model)
         self._trunk(model, B, Hp, Wp)
-        self._dense_depth_head(model)
+        self._check_level_sizes()
+        self._dense_depth_head(model, keep_tower_outputs=self.keep_tower_outputs, batch_stats=self.batch_stats)
         dev, feats = self.device, self.features
         L = len(feats)
         if L > hip.MAX_LEVELS:
@@ -121,9 +134,9 @@ class DenseDepthLossPlan(DenseDepthPlan):
         self.loss_args = a
         self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_dense_depth_loss(C.byref(a), st), "dense_depth_loss"), "dense_depth_loss",
                                dict(kind="dense_depth_loss")))
-        self.grads = bool(head_grads)
         if self.grads:
             self._loss_grads(a)
+        self._backward_chain(model)
 
     def _loss_grads(self, a):
         """Gradient buffers shaped like the raw maps (zeros: the kernel writes channel 0 only), the upstream vector and the slab."""
@@ -134,6 +147,13 @@ class DenseDepthLossPlan(DenseDepthPlan):
         self.grad_args = g
         self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_dense_depth_loss_backward(C.byref(a), C.byref(g), st), "dense_depth_loss_backward"),
                                "dense_depth_loss_backward", dict(kind="dense_depth_loss_backward")))
+
+    def _pred_group_table(self, model):
+        """The one predictor group for BackwardStages._pred_grads: g = d_raw, maps = dd_raw, the per-level filters of
+        fcos3d_head.dense_depth; with USE_SCALE slot 0 is scales_depth / offsets_depth, else the conv bias takes the gradient."""
+        head = model.fcos3d_head
+        slots = [(0, 1, 0, head.scales_depth, head.offsets_depth)] if head.use_scale else []
+        return ("box3d", ), {"dd_raw": slots}, {"dd_raw": self.d_raw}, {"dd_raw": self.dd_raw}
 
     def head_grads(self):
         """The gradients of the last run: {"dense_depth<l>": (B, 1, h_l, w_l) float32} (copies), with respect to the head's per-level

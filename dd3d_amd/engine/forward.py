@@ -132,10 +132,10 @@ class ForwardPlan(PlanBase, BackboneLowering):
         return t[..., :3].permute(0, 3, 1, 2)
 
     # ------------------------------------------------------------------ heads (fcos2d.py:130-156, fcos3d.py:160-188)
-    def _bn_tower_layer(self, i, bn_segs, Cf):
+    def _bn_tower_layer(self, i, bn_segs, Cf, prefix="towers"):
         """The three ops of a tower depth's batch-statistics segments behind their raw convolution (LossPlan(batch_stats=True)):
         `bn_segs`: (tower name, tower index, level, conv, norm, input view, raw view, output view).  Returns {(tower name, level): the
-        segment's index}, the dd3d_tower_bn_args and the statistics tensor [segments, BN_STAT_ROWS, Cf]."""
+        segment's index}, the dd3d_tower_bn_args and the statistics tensor [segments, BN_STAT_ROWS, Cf].  `prefix`: of the ops' names."""
         dev = self.device
         a = hip.TowerBnArgs()
         n = len(bn_segs)
@@ -163,12 +163,12 @@ class ForwardPlan(PlanBase, BackboneLowering):
         a.eps, a.momentum, a.plane_scale = float(bn_segs[0][4].eps), hip.BN_MOMENTUM, float(bn_segs[0][-1].buf.plane_scale)
         self.tower_bn_args.append(a)
         desc = dict(segs=[dict(tower=tname, level=l, raw=raw, out=out, norm=norm) for tname, _, l, _, norm, _, raw, out in bn_segs], stats=stats)
-        op = CallOp(lambda lib, st, a=a: hip.check(lib.dd3d_bn_batch_stats(C.byref(a), st), f"bn_batch_stats {i}"), f"towers.{i}.bn_stats",
+        op = CallOp(lambda lib, st, a=a: hip.check(lib.dd3d_bn_batch_stats(C.byref(a), st), f"bn_batch_stats {i}"), f"{prefix}.{i}.bn_stats",
                     dict(desc, kind="bn_batch_stats"))
         op.keep = keep
         self.ops.append(op)
         self.ops.append(CallOp(lambda lib, st, a=a: hip.check(lib.dd3d_bn_apply_relu_split(C.byref(a), st), f"bn_apply_relu_split {i}"),
-                               f"towers.{i}.bn_apply", dict(desc, kind="bn_apply_relu_split", planes=planes)))
+                               f"{prefix}.{i}.bn_apply", dict(desc, kind="bn_apply_relu_split", planes=planes)))
         return index, a, stats
 
     def _heads(self, model, feats, keep_tower_outputs=False, batch_stats=False):
@@ -643,26 +643,59 @@ class DenseDepthPlan(ForwardPlan):
             self.ops.append(CallOp(_up, f"dd_upsample.{l}", dict(kind="aligned_bilinear_scale", src=self.dd_raw[l], out=o, factor=stride,
                                                                    offset_half=half, focal_factor=factor)))
 
-    def _dense_depth_head(self, model):
+    def _dense_depth_head(self, model, keep_tower_outputs=False, batch_stats=False):
         """The box3d tower and the per-level predictors on the trunk's features (shared with DenseDepthLossPlan): `dd_raw`, the raw
-        1-channel maps (NHWC f32, pitch 4) the up-sampling reads."""
+        1-channel maps (NHWC f32, pitch 4) the up-sampling reads.  What `_heads` records for the backward (engine.losses) is recorded
+        here in the same form: `tower_info` when `keep_tower_outputs` gives every tower layer an output buffer of its own, `pred_info` and
+        `tower_out` for the one predictor group (a filter per level, n = 1 at pitch 4, no clamp), `tower_bn` for the layers that
+        `batch_stats` takes out of the fused launch (raw convolution, statistics, apply: `_bn_tower_layer`)."""
+        from dd3d_amd.layers import BatchNorm2d
         feats, head = self.features, model.fcos3d_head
         L, Cf = len(feats), feats[0].C
-        ping = [self.buf(f"ddA.{l}", f.B, f.H, f.W, Cf, kind="planes") for l, f in enumerate(feats)]
-        pong = [self.buf(f"ddB.{l}", f.B, f.H, f.W, Cf, kind="planes") for l, f in enumerate(feats)]
+        keep_all = bool(keep_tower_outputs)
+        tbuf = lambda name: [self.buf(f"{name}.{l}", f.B, f.H, f.W, Cf, kind="planes") for l, f in enumerate(feats)]
+        if not keep_all:
+            ping, pong = tbuf("ddA"), tbuf("ddB")
+        level_norm = lambda conv, l: conv.norm[l] if isinstance(conv.norm, torch.nn.ModuleList) else conv.norm
+        is_bn = lambda conv: bool(batch_stats) and all(isinstance(level_norm(conv, l), BatchNorm2d) for l in range(L))
+        self.tower_info = {} if keep_all else None
+        self.tower_bn, self.tower_bn_args, self.bn_part = OrderedDict(), [], None
+        raw_bufs = None
         cur = list(feats)
         for i, conv in enumerate(head.box3d_tower):
-            dst = ping if i % 2 == 0 else pong
+            dst = tbuf(f"ddL{i}") if keep_all else ping if i % 2 == 0 else pong
             w, meta = self.pack(conv.weight)
-            segs = []
+            bn = is_bn(conv)
+            if bn and (keep_all or raw_bufs is None):  # a plan that keeps the tower outputs keeps every layer's raw output too
+                raw_bufs = [self.buf(f"ddraw{i}.{l}" if keep_all else f"ddraw.{l}", f.B, f.H, f.W, Cf) for l, f in enumerate(feats)]
+            info = dict(conv=conv, index=0, norms=[], scales=[], x=[], y=[], raw=[] if bn else None)
+            if keep_all:
+                self.tower_info[("box3d", i)] = info
+            segs, bn_segs = [], []
             for l in range(L):
-                norm = conv.norm[l] if isinstance(conv.norm, torch.nn.ModuleList) else conv.norm
-                scale, shift = fold_norm(conv, norm)
-                segs.append({"in": cur[l], "out": dst[l].view(), "w": w, "scale": self._vec(scale), "bias": self._vec(shift)})
-                cur[l] = dst[l].view()
-            self.ops.append(ConvOp(self, meta, 1, 1, segs, relu=True, name=f"dd_tower.{i}"))
+                norm, out = level_norm(conv, l), dst[l].view()
+                if bn:  # epilogue: scale ones, the conv bias or zeros (as _heads)
+                    raw = raw_bufs[l].view()
+                    shift = conv.bias.detach().float().cpu() if conv.bias is not None else torch.zeros(Cf)
+                    segs.append({"in": cur[l], "out": raw, "w": w, "scale": self._vec(torch.ones(Cf)), "bias": self._vec(shift)})
+                    bn_segs.append(("box3d", 0, l, conv, norm, cur[l], raw, out))
+                    info["raw"].append(raw)
+                else:
+                    scale, shift = fold_norm(conv, norm)
+                    segs.append({"in": cur[l], "out": out, "w": w, "scale": self._vec(scale), "bias": self._vec(shift)})
+                info["scales"].append(segs[-1]["scale"])
+                info["norms"].append(norm), info["x"].append(cur[l]), info["y"].append(out)
+                cur[l] = out
+            if bn:
+                self.ops.append(ConvOp(self, meta, 1, 1, segs, relu=False, name=f"dd_tower.{i}.raw"))
+                index, args, stats = self._bn_tower_layer(i, bn_segs, Cf, prefix="dd_tower")
+                self.tower_bn[("box3d", i)] = dict(conv=conv, norms=[level_norm(conv, l) for l in range(L)], stats=stats, args=args,
+                                                   segs=[index[("box3d", l)] for l in range(L)])
+            else:
+                self.ops.append(ConvOp(self, meta, 1, 1, segs, relu=True, name=f"dd_tower.{i}"))
+        self.tower_out = [[v] for v in cur]
         # predictors: a different filter per level (dense_depth.py:63-67,93-97), (conv + b) * scale + offset
-        segs, self.dd_raw = [], []
+        segs, self.dd_raw, scales = [], [], []
         meta = None
         for l, conv in enumerate(head.dense_depth):
             w, meta = self.pack(conv.weight)
@@ -671,5 +704,7 @@ class DenseDepthPlan(ForwardPlan):
             off = head.offsets_depth[l].bias.detach().float().cpu() if head.use_scale else torch.zeros(1)
             out = self.buf(f"dd_raw.{l}", feats[l].B, feats[l].H, feats[l].W, 4)
             self.dd_raw.append(out)
+            scales.append(sc.reshape(1))
             segs.append({"in": cur[l], "out": out.view(0, 4), "w": w, "scale": self._vec(sc), "bias": self._vec(b * sc + off), "n_limit": 1})
         self.ops.append(ConvOp(self, meta, 1, 1, segs, relu=False, name="dd_predictors"))
+        self.pred_info = {"dd_raw": dict(convs=[list(head.dense_depth)], tower=0, n=1, pitch=4, lo=None, scales=scales)}

@@ -7,7 +7,8 @@ and the stem's output (csrc/backbone_grads.hip), and last through the stem -- ba
 (csrc/stem_grads.hip); for the VoVNet-V2 backbones, behind the FPN through stage5 .. stage2, stem_3 and stem_2 (csrc/vovnet_grads.hip and
 the wide entry points of csrc/backbone_grads.hip) and last stem_1's filter (dd3d_vovnet_stem_wgrad, csrc/stem_grads.hip).  With
 batch_stats=True the head towers whose norm is a trainable BatchNorm2d use the batch's statistics, forward and backward
-(csrc/tower_bn.hip).  There is no optimiser or model.train().
+(csrc/tower_bn.hip).  There is no optimiser or model.train().  The chain behind the loss backward (flags, stage builders, read-outs) is the
+mixin ``BackwardStages``: ``LossPlan`` and the dense-depth network's ``DenseDepthLossPlan`` (dense_depth_loss.py) both run it.
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
 runs two launches of csrc/losses.hip: the assignment (DD3DTargetPreparer, prepare_targets.py:28-235) and the per-target loss terms with
@@ -1179,11 +1180,14 @@ def assemble_tower_grads(model, layers, feature_grads):
     return feats, params
 
 
-class LossPlan(ForwardPlan):
-    """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
-    hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
-    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
-                 fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False):
+class BackwardStages:
+    """The backward chain behind a loss plan's own backward call, shared by LossPlan and DenseDepthLossPlan (dense_depth_loss.py): the
+    flags with their implications and early refusals, the stage builders from the predictor groups down to the stems, and the read-outs.
+    A plan mixes this in beside its forward plan; what it must provide: `tower_info`, `tower_out`, `pred_info`, `tower_bn` / `bn_part` as
+    ForwardPlan._heads records them, `_pred_group_table` (what the predictor groups bind), and `grads` handled by its own loss backward."""
+    def _chain_flags(self, model, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
+                     stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False):
+        """The flags of the chain, each implying the shallower ones, and what they refuse before anything is built or launched."""
         self.batch_stats = bool(batch_stats)
         if self.batch_stats:  # before anything is built or launched
             check_batch_stats(model, B, Hp, Wp)
@@ -1199,71 +1203,20 @@ class LossPlan(ForwardPlan):
         if self.with_stem_grads and (int(Hp) % 2 or int(Wp) % 2):
             raise NotImplementedError(f"stem gradients need an even canvas ({Hp} x {Wp}): the stem's lowering sizes level1 as floor(H / 2), the stride-2 "
                                       "backward as ceil(H / 2); canvases padded to the FPN's size divisibility are always even")
-        PlanBase.__init__(self, device or model.device, dry_run=dry_run)
         self.with_fpn_grads = bool(fpn_grads) or self.with_backbone_grads or self.with_vovnet_grads
         self.keep_tower_outputs = bool(tower_grads) or self.with_fpn_grads
         self.pred_grads = bool(pred_grads) or self.keep_tower_outputs
         self.grads = bool(grads) or self.pred_grads
-        check_loss_config(model.cfg)
-        from dd3d_amd.engine.tiling import default_tile_policy
-        self.tile_policy = default_tile_policy() or getattr(model, "tile_policy", None) or "latency"  # as ForwardPlan: the forward's own tiles
-        self.exchange, self.camera_sharded, self.has_bev_inputs = False, False, False
-        self.adopt_weight_store(model)
-        self._trunk(model, B, Hp, Wp)
+
+    def _check_level_sizes(self):
+        """Under batch_stats, behind the trunk: check_batch_stats predicted the level sizes; these are the plan's own."""
         if self.batch_stats:
             small = [(f.H, f.W) for f in self.features if f.B * f.H * f.W < 2]
-            if small:  # (check_batch_stats predicted the level sizes; these are the plan's own)
-                raise ValueError(f"Expected more than 1 value per channel when training, got a {small[0][0]} x {small[0][1]} level with a batch of {B}")
-        self._heads(model, self.features, keep_tower_outputs=self.keep_tower_outputs, batch_stats=self.batch_stats)
-        self._losses(model, max_gt)
+            if small:
+                raise ValueError(f"Expected more than 1 value per channel when training, got a {small[0][0]} x {small[0][1]} level with a batch of {self.B}")
 
-    def _losses(self, model, max_gt):
-        cfg, dev, B = model.cfg, self.device, self.B
-        feats = self.features
-        L = len(feats)
-        self.box3d_on, self.nusc = self.b3d_maps is not None, model_is_nusc(model)
-        self.max_gt = int(max_gt)
-        a = hip.LossArgs()
-        level_hw = [(f.H, f.W) for f in feats]
-        self.level_sizes = [h * w for h, w in level_hw]
-        nloc = _fill_common(a, cfg, model, level_hw, self.strides, B, max_gt)
-        off = model.feature_locations_offset
-        self.locations = torch.cat([feature_locations(h, w, self.strides[l], off) for l, (h, w) in enumerate(level_hw)]).to(dev)
-        for l in range(L):
-            a.cls[l] = self.cls_maps[l].t.data_ptr()
-            a.box2d[l] = self.b2d_maps[l].t.data_ptr()
-            a.box3d[l] = self.b3d_maps[l].t.data_ptr() if self.box3d_on else None
-        a.cls_pitch, a.b2d_pitch, a.b3d_pitch = self.cls_pitch, self.b2d_pitch, self.b3d_pitch
-        a.attr_off, a.num_attr, a.speed_off = 0, 0, -1
-        if self.nusc:  # nuScenes extras ride on the cls map (ForwardPlan._heads)
-            a.attr_off, a.num_attr = model.num_classes, num_attributes(model)
-            a.speed_off = model.num_classes + a.num_attr
-        if self.box3d_on:
-            self.canon = torch.tensor([list(r) for r in cfg.DD3D.FCOS3D.CANONICAL_BOX3D_SIZES], dtype=torch.float32, device=dev)
-            a.canon_sizes = self.canon.data_ptr()
-        a.inv_K = self.inv_K.data_ptr()  # written by the trunk's first launch (K^-1 of the images, core.py:93)
-        a.locations = self.locations.data_ptr()
-        # GT staging: [offsets B + 1 (int32), padded to 4 words | records B * max_gt * LOSS_GT_FIELDS], pinned mirror + device twin
-        self.gt_hdr = (B + 1 + 3) // 4 * 4
-        words = self.gt_hdr + B * self.max_gt * hip.LOSS_GT_FIELDS
-        self.host_gt = self.host_buf(words, torch.float32)
-        self.dev_gt = torch.zeros(words, dtype=torch.float32, device=dev)
-        self._gt_words = self.gt_hdr
-        a.gt_off, a.gt = self.dev_gt.data_ptr(), self.dev_gt.data_ptr() + 4 * self.gt_hdr
-        N = B * nloc
-        self.targets = _Targets(a, N, self.box3d_on, self.nusc, dev)
-        nblocks = (N + hip.LOSS_BLOCK - 1) // hip.LOSS_BLOCK
-        self.partials = torch.zeros((nblocks, hip.LOSS_TERMS), dtype=torch.float32, device=dev)
-        self.loss_out = torch.zeros(hip.LOSS_OUT, dtype=torch.float32, device=dev)
-        self.det_count = torch.zeros(1, dtype=torch.int32, device=dev)  # the positive count, in the read-back record
-        a.partials, a.n_partials, a.out, a.num_pos = self.partials.data_ptr(), nblocks, self.loss_out.data_ptr(), self.det_count.data_ptr()
-        self.loss_args = a
-        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_assign(C.byref(a), st), "loss_assign"), "loss_assign",
-                               dict(kind="loss_assign")))
-        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_terms(C.byref(a), st), "loss_terms"), "loss_terms",
-                               dict(kind="loss_terms")))
-        if self.grads:
-            self._loss_grads(a)
+    def _backward_chain(self, model):
+        """The stages the flags ask for, behind the plan's loss backward, in their order."""
         if self.pred_grads:
             self._pred_grads(model)
         if self.keep_tower_outputs:
@@ -1279,34 +1232,18 @@ class LossPlan(ForwardPlan):
         if self.with_vovnet_stem_grads:
             self._vovnet_stem_grads(model)
 
-    def _loss_grads(self, a):
-        """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
-        more launch, dd3d_loss_backward, behind the loss terms -- still one hipGraph."""
-        like = lambda maps: [torch.zeros_like(m.t) for m in maps]
-        self.d_cls, self.d_b2d = like(self.cls_maps), like(self.b2d_maps)
-        self.d_b3d = like(self.b3d_maps) if self.box3d_on else None
-        self.upstream = torch.ones(hip.LOSS_OUT, dtype=torch.float32, device=self.device)
-        self.grad_denoms = torch.zeros(hip.LOSS_GRAD_DENOMS, dtype=torch.float32, device=self.device)
-        g = fill_grad_args(self.d_cls, self.d_b2d, self.d_b3d, self.upstream, self.grad_denoms)
-        self.grad_args = g
-        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_backward(C.byref(a), C.byref(g), st), "loss_backward"), "loss_backward",
-                               dict(kind="loss_backward")))
+    def _built_without(self, flag):
+        return RuntimeError(f"this {type(self).__name__} was built without {flag}=True")
 
     def _pred_grads(self, model):
-        """The predictor layer's backward behind dd3d_loss_backward, one weight-gradient and one input-gradient call per predictor group
-        (= per tower) on the main stream -- still one hipGraph."""
+        """The predictor layer's backward behind the plan's loss backward, one weight-gradient and one input-gradient call per predictor
+        group (= per tower) on the main stream -- still one hipGraph.  `_pred_group_table` names the towers and gives per group of
+        `pred_info` its slots -- (first channel, channels, slot, Scale list, Offset list) of the per-level scalars --, the gradient buffers
+        at its maps and the maps."""
         dev, L = self.device, len(self.features)
         mode = pred_act_mode(self)
-        h2, h3 = model.fcos2d_head, (None if model.only_box2d else model.fcos3d_head)
         level_hw = [(f.H, f.W) for f in self.features]
-        C3 = (1 if h3.class_agnostic else int(model.num_classes)) if h3 is not None else 0
-        # (first channel, channels, slot, Scale list, Offset list) of the per-level scalars of a group
-        slots = {"cls_map": [], "box2d_map": [(0, 4, 0, h2.scales_box2d_reg, None)] if h2.use_scale else [], "box3d_map": []}
-        if h3 is not None and h3.use_scale:
-            slots["box3d_map"] = [(4 * C3, 2 * C3, 0, h3.scales_proj_ctr, None), (6 * C3, C3, 1, h3.scales_depth, h3.offsets_depth),
-                                  (7 * C3, 3 * C3, 2, h3.scales_size, None), (10 * C3, C3, 3, h3.scales_conf, None)]
-        grads = {"cls_map": self.d_cls, "box2d_map": self.d_b2d, "box3d_map": self.d_b3d}
-        maps = {"cls_map": self.cls_maps, "box2d_map": self.b2d_maps, "box3d_map": self.b3d_maps}
+        tower_names, slots, grads, maps = self._pred_group_table(model)
         self.pred_groups = {}
         for name, info in self.pred_info.items():
             n, t = info["n"], info["tower"]
@@ -1329,7 +1266,7 @@ class LossPlan(ForwardPlan):
             grp = PredGroupGrads(dev, self.B, level_hw, Cin, n, info["pitch"], act, mode, tv[0].pitch, tv[0].buf.plane_scale,
                                  grads[name], [m.t for m in maps[name]], w, bias, [self._vec(sc) for sc in info["scales"]],
                                  lo=None if info["lo"] is None else self._vec(info["lo"]), slot=slot.to(dev))
-            grp.convs, grp.slots, grp.tower = info["convs"], slots[name], ("cls", "box2d", "box3d")[t]
+            grp.convs, grp.slots, grp.tower = info["convs"], slots[name], tower_names[t]
             self.pred_groups[name] = grp
             self.ops.append(CallOp(lambda lib, st, grp=grp: grp.launch(lib, st), "predictor_grads." + name,
                                    dict(kind="predictor_grads", group=name)))
@@ -1338,7 +1275,7 @@ class LossPlan(ForwardPlan):
         """(tower-output gradients, parameter gradients) of the last run, copies: {<tower>_tower_out<l>: (B, Cin, h_l, w_l)} and
         {name in model.named_parameters(): tensor of the parameter's shape}, float32."""
         if not self.pred_grads:
-            raise RuntimeError("this LossPlan was built without pred_grads=True")
+            raise self._built_without("pred_grads")
         names = self._named()
         towers, params = {}, {}
         for grp in self.pred_groups.values():
@@ -1507,7 +1444,7 @@ class LossPlan(ForwardPlan):
         """(backbone-feature gradients, FPN parameter gradients) of the last run, copies: {backbone_<name>: (B, C_name, h, w)} and {name in
         model.named_parameters(): tensor of the parameter's shape}, float32; the gradients of the buffers' pad channels are dropped."""
         if not self.with_fpn_grads:
-            raise RuntimeError("this LossPlan was built without fpn_grads=True")
+            raise self._built_without("fpn_grads")
         feats = {f"backbone_{n}": d[..., :c].permute(0, 3, 1, 2).clone() for n, (d, c) in self.backbone_feature_grads.items()}
         return feats, fpn_param_grads(self._named(), self.fpn_layers)
 
@@ -1535,7 +1472,7 @@ class LossPlan(ForwardPlan):
         Hp / 2, Wp / 2)} -- not yet masked by that tensor's own ReLU -- and {name in model.named_parameters(): tensor of the parameter's
         shape} for every parameter of backbone.bottom_up.level2 .. level5, float32."""
         if not self.with_backbone_grads:
-            raise RuntimeError("this LossPlan was built without backbone_grads=True")
+            raise self._built_without("backbone_grads")
         return {"backbone_level1": self.level1_grad.permute(0, 3, 1, 2).clone()}, dla_param_grads(self._named(), self.backbone_layers)
 
     def _stem_grads(self, model):
@@ -1573,7 +1510,7 @@ class LossPlan(ForwardPlan):
         {backbone_level0, backbone_base_layer: (B, 16, Hp, Wp)} -- neither masked by its tensor's own ReLU yet -- and {name in
         model.named_parameters(): tensor of the parameter's shape} for backbone.bottom_up.base_layer / level0.0 / level1.0, float32."""
         if not self.with_stem_grads:
-            raise RuntimeError("this LossPlan was built without stem_grads=True")
+            raise self._built_without("stem_grads")
         tens = {"backbone_level0": self.stem_layers["level1.0"].da.permute(0, 3, 1, 2).clone(),
                 "backbone_base_layer": self.stem_layers["level0.0"].da.permute(0, 3, 1, 2).clone()}
         return tens, dla_param_grads(self._named(), self.stem_layers)
@@ -1608,7 +1545,7 @@ class LossPlan(ForwardPlan):
         Wp / 2)} -- not yet masked by that tensor's own ReLU -- and {name in model.named_parameters(): tensor of the parameter's shape} for
         every parameter of backbone.bottom_up but stem.stem_1/* (those: vovnet_stem_grads), float32."""
         if not self.with_vovnet_grads:
-            raise RuntimeError("this LossPlan was built without vovnet_grads=True")
+            raise self._built_without("vovnet_grads")
         return {"backbone_stem_1": self.stem1_grad.permute(0, 3, 1, 2).clone()}, vovnet_param_grads(self._named(), self.vovnet_layers)
 
     def _vovnet_stem_grads(self, model):
@@ -1642,7 +1579,7 @@ class LossPlan(ForwardPlan):
         channel's column is dropped) and, for a BN backbone on running statistics, stem.stem_1/norm.weight and .bias; FrozenBN owns
         nothing.  With vovnet_grads' these are the parameters of named_parameters()."""
         if not self.with_vovnet_stem_grads:
-            raise RuntimeError("this LossPlan was built without vovnet_stem_grads=True")
+            raise self._built_without("vovnet_stem_grads")
         lay = self.vovnet_stem_layers["stem_1"]
         return {}, conv_param_grads(self._named(), lay, lay.conv, lay.norm, lay.dw, lay.scale, lay.q, lay.r)
 
@@ -1651,7 +1588,7 @@ class LossPlan(ForwardPlan):
         model.named_parameters(): tensor of the parameter's shape}, float32.  A filter's gradient is the kernels' dw; the few per-channel
         products of a norm's weight (rstd * (r + (b_conv - mean) * q)) and the sums of q over the levels are torch ops here."""
         if not self.keep_tower_outputs:
-            raise RuntimeError("this LossPlan was built without tower_grads=True")
+            raise self._built_without("tower_grads")
         return assemble_tower_grads(self.model, self.tower_layers, self.feature_grads)
 
     def tower_batch_stats(self):
@@ -1660,7 +1597,7 @@ class LossPlan(ForwardPlan):
         ((1 - 0.1) * running + 0.1 * batch, the variance unbiased by N / (N - 1)), under `.batch_mean` / `.batch_var` the batch's mean
         and biased variance.  The model's own buffers are never written."""
         if not self.batch_stats:
-            raise RuntimeError("this LossPlan was built without batch_stats=True")
+            raise self._built_without("batch_stats")
         names = {id(b): k for k, b in self.model.named_buffers()}
         out = {}
         for rec in self.tower_bn.values():
@@ -1672,10 +1609,106 @@ class LossPlan(ForwardPlan):
                 out[stem + "batch_mean"], out[stem + "batch_var"] = st[hip.BN_ROW_MU].clone(), st[hip.BN_ROW_VAR].clone()
         return out
 
+
+class LossPlan(BackwardStages, ForwardPlan):
+    """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
+    hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
+    def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
+                 fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False):
+        self._chain_flags(model, B, Hp, Wp, grads=grads, pred_grads=pred_grads, tower_grads=tower_grads, fpn_grads=fpn_grads,
+                          backbone_grads=backbone_grads, stem_grads=stem_grads, vovnet_grads=vovnet_grads, batch_stats=batch_stats,
+                          vovnet_stem_grads=vovnet_stem_grads)
+        PlanBase.__init__(self, device or model.device, dry_run=dry_run)
+        check_loss_config(model.cfg)
+        from dd3d_amd.engine.tiling import default_tile_policy
+        self.tile_policy = default_tile_policy() or getattr(model, "tile_policy", None) or "latency"  # as ForwardPlan: the forward's own tiles
+        self.exchange, self.camera_sharded, self.has_bev_inputs = False, False, False
+        self.adopt_weight_store(model)
+        self._trunk(model, B, Hp, Wp)
+        self._check_level_sizes()
+        self._heads(model, self.features, keep_tower_outputs=self.keep_tower_outputs, batch_stats=self.batch_stats)
+        self._losses(model, max_gt)
+
+    def _losses(self, model, max_gt):
+        cfg, dev, B = model.cfg, self.device, self.B
+        feats = self.features
+        L = len(feats)
+        self.box3d_on, self.nusc = self.b3d_maps is not None, model_is_nusc(model)
+        self.max_gt = int(max_gt)
+        a = hip.LossArgs()
+        level_hw = [(f.H, f.W) for f in feats]
+        self.level_sizes = [h * w for h, w in level_hw]
+        nloc = _fill_common(a, cfg, model, level_hw, self.strides, B, max_gt)
+        off = model.feature_locations_offset
+        self.locations = torch.cat([feature_locations(h, w, self.strides[l], off) for l, (h, w) in enumerate(level_hw)]).to(dev)
+        for l in range(L):
+            a.cls[l] = self.cls_maps[l].t.data_ptr()
+            a.box2d[l] = self.b2d_maps[l].t.data_ptr()
+            a.box3d[l] = self.b3d_maps[l].t.data_ptr() if self.box3d_on else None
+        a.cls_pitch, a.b2d_pitch, a.b3d_pitch = self.cls_pitch, self.b2d_pitch, self.b3d_pitch
+        a.attr_off, a.num_attr, a.speed_off = 0, 0, -1
+        if self.nusc:  # nuScenes extras ride on the cls map (ForwardPlan._heads)
+            a.attr_off, a.num_attr = model.num_classes, num_attributes(model)
+            a.speed_off = model.num_classes + a.num_attr
+        if self.box3d_on:
+            self.canon = torch.tensor([list(r) for r in cfg.DD3D.FCOS3D.CANONICAL_BOX3D_SIZES], dtype=torch.float32, device=dev)
+            a.canon_sizes = self.canon.data_ptr()
+        a.inv_K = self.inv_K.data_ptr()  # written by the trunk's first launch (K^-1 of the images, core.py:93)
+        a.locations = self.locations.data_ptr()
+        # GT staging: [offsets B + 1 (int32), padded to 4 words | records B * max_gt * LOSS_GT_FIELDS], pinned mirror + device twin
+        self.gt_hdr = (B + 1 + 3) // 4 * 4
+        words = self.gt_hdr + B * self.max_gt * hip.LOSS_GT_FIELDS
+        self.host_gt = self.host_buf(words, torch.float32)
+        self.dev_gt = torch.zeros(words, dtype=torch.float32, device=dev)
+        self._gt_words = self.gt_hdr
+        a.gt_off, a.gt = self.dev_gt.data_ptr(), self.dev_gt.data_ptr() + 4 * self.gt_hdr
+        N = B * nloc
+        self.targets = _Targets(a, N, self.box3d_on, self.nusc, dev)
+        nblocks = (N + hip.LOSS_BLOCK - 1) // hip.LOSS_BLOCK
+        self.partials = torch.zeros((nblocks, hip.LOSS_TERMS), dtype=torch.float32, device=dev)
+        self.loss_out = torch.zeros(hip.LOSS_OUT, dtype=torch.float32, device=dev)
+        self.det_count = torch.zeros(1, dtype=torch.int32, device=dev)  # the positive count, in the read-back record
+        a.partials, a.n_partials, a.out, a.num_pos = self.partials.data_ptr(), nblocks, self.loss_out.data_ptr(), self.det_count.data_ptr()
+        self.loss_args = a
+        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_assign(C.byref(a), st), "loss_assign"), "loss_assign",
+                               dict(kind="loss_assign")))
+        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_terms(C.byref(a), st), "loss_terms"), "loss_terms",
+                               dict(kind="loss_terms")))
+        if self.grads:
+            self._loss_grads(a)
+        self._backward_chain(model)
+
+    def _loss_grads(self, a):
+        """Gradient buffers shaped like the head maps, the upstream vector (ones: the gradient of the sum of the dict's values) and one
+        more launch, dd3d_loss_backward, behind the loss terms -- still one hipGraph."""
+        like = lambda maps: [torch.zeros_like(m.t) for m in maps]
+        self.d_cls, self.d_b2d = like(self.cls_maps), like(self.b2d_maps)
+        self.d_b3d = like(self.b3d_maps) if self.box3d_on else None
+        self.upstream = torch.ones(hip.LOSS_OUT, dtype=torch.float32, device=self.device)
+        self.grad_denoms = torch.zeros(hip.LOSS_GRAD_DENOMS, dtype=torch.float32, device=self.device)
+        g = fill_grad_args(self.d_cls, self.d_b2d, self.d_b3d, self.upstream, self.grad_denoms)
+        self.grad_args = g
+        self.ops.append(CallOp(lambda lib, st: hip.check(lib.dd3d_loss_backward(C.byref(a), C.byref(g), st), "loss_backward"), "loss_backward",
+                               dict(kind="loss_backward")))
+
+    def _pred_group_table(self, model):
+        """The FCOS heads' predictor groups for BackwardStages._pred_grads: (tower names by index, {group: slots}, {group: gradient buffers},
+        {group: maps})."""
+        h2, h3 = model.fcos2d_head, (None if model.only_box2d else model.fcos3d_head)
+        C3 = (1 if h3.class_agnostic else int(model.num_classes)) if h3 is not None else 0
+        # (first channel, channels, slot, Scale list, Offset list) of the per-level scalars of a group
+        slots = {"cls_map": [], "box2d_map": [(0, 4, 0, h2.scales_box2d_reg, None)] if h2.use_scale else [], "box3d_map": []}
+        if h3 is not None and h3.use_scale:
+            slots["box3d_map"] = [(4 * C3, 2 * C3, 0, h3.scales_proj_ctr, None), (6 * C3, C3, 1, h3.scales_depth, h3.offsets_depth),
+                                  (7 * C3, 3 * C3, 2, h3.scales_size, None), (10 * C3, C3, 3, h3.scales_conf, None)]
+        grads = {"cls_map": self.d_cls, "box2d_map": self.d_b2d, "box3d_map": self.d_b3d}
+        maps = {"cls_map": self.cls_maps, "box2d_map": self.b2d_maps, "box3d_map": self.b3d_maps}
+        return ("cls", "box2d", "box3d"), slots, grads, maps
+
     def head_grads(self):
         """The gradients of the last run as NCHW per-level tensors (copies) under the keys of the reference's head maps."""
         if not self.grads:
-            raise RuntimeError("this LossPlan was built without grads=True")
+            raise self._built_without("grads")
         return unpack_head_grads(self.d_cls, self.d_b2d, self.d_b3d, int(self.model.num_classes), self.loss_args.num_attr if self.nusc else 0,
                                  bool(self.loss_args.class_agnostic_3d))
 

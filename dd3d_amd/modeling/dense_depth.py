@@ -6,13 +6,14 @@ The reference's ``forward`` only defines the training branch (it ends in ``raise
 dense_depth.py:162-163); everything it computes before the losses is inference math, exposed here as
 ``predict_dense_depth(batched_inputs)``; ``forward`` keeps the reference's eval-mode behaviour.  What the training branch adds, the
 per-level loss dict (dense_depth.py:165-171), is ``compute_losses(batched_inputs)``; with ``head_grads=True`` also the gradient with
-respect to the head's per-level maps (no backward through the convolutions).
+respect to the head's per-level maps, and with the deeper flags of ``DD3D.compute_losses`` (``predictor_grads`` .. ``stem_grads``,
+``vovnet_grads`` / ``vovnet_stem_grads``) the gradient of every parameter, through the same backward stages as the detector's.
 """
 import torch
 from torch import nn
 
 from dd3d_amd.layers import Conv2d, Offset, Scale
-from dd3d_amd.modeling.dd3d import build_feature_extractor
+from dd3d_amd.modeling.dd3d import _deepest, build_feature_extractor
 from dd3d_amd.modeling.heads import _init_predictor, _init_tower, _make_tower
 from dd3d_amd.registry import META_ARCH_REGISTRY
 
@@ -154,45 +155,91 @@ class DD3DDenseDepth(nn.Module):
         plan.check_status()  # one 4-byte read behind the forward (the caller is about to consume the maps anyway); raises and clears
         return [m for m in plan.depth_maps]
 
-    def get_loss_plan(self, B, Hp, Wp, head_grads=False):
+    def get_loss_plan(self, B, Hp, Wp, head_grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
+                      stem_grads=False, vovnet_grads=False, vovnet_stem_grads=False, **norms):
         """The loss plan (engine.DenseDepthLossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the
-        prediction plans, under a key of its own (another one with `head_grads`: the backward call is part of that plan's graph)."""
+        prediction plans, under a key of its own (another one with `head_grads`: the backward call is part of that plan's graph).  The
+        deeper flags are DD3D.get_loss_plan's, each implying the shallower ones: one plan, and one cache key, per deepest requested level
+        of the backward, and a further key under `batch_stats=True` (the box3d tower's trainable BatchNorm2d on the batch's statistics;
+        the keyword is taken from `**norms`, any other extra keyword is a TypeError)."""
         from dd3d_amd.engine import DenseDepthLossPlan
-        if head_grads:
-            return self._cached_plan(("dense_depth_loss_grads", B, Hp, Wp, self.math), lambda: DenseDepthLossPlan(self, B, Hp, Wp, head_grads=True))
-        return self._cached_plan(("dense_depth_loss", B, Hp, Wp, self.math), lambda: DenseDepthLossPlan(self, B, Hp, Wp))
+        batch_stats = bool(norms.pop("batch_stats", False))
+        if norms:
+            raise TypeError(f"get_loss_plan() got an unexpected keyword argument {next(iter(norms))!r}")
+        level = _deepest(vovnet_stem_grads=vovnet_stem_grads, vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads,
+                         fpn_grads=fpn_grads, tower_grads=tower_grads, pred_grads=pred_grads, head_grads=head_grads)
+        if not batch_stats and not set(level) - {"head_grads"}:  # the two keys from before the deeper levels existed
+            return self._cached_plan(("dense_depth_loss_grads" if level else "dense_depth_loss", B, Hp, Wp, self.math),
+                                     lambda: DenseDepthLossPlan(self, B, Hp, Wp, **level))
+        key = ("dense_depth_loss", B, Hp, Wp, self.math) + tuple(level)
+        if batch_stats:
+            key, level = key + ("batch_stats", ), dict(level, batch_stats=True)
+        return self._cached_plan(key, lambda: DenseDepthLossPlan(self, B, Hp, Wp, **level))
 
     @torch.no_grad()
-    def compute_losses(self, batched_inputs, head_grads=False):
+    def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
+                       stem_grads=False, **branch):
         """The loss dict of the reference's training forward (dense_depth.py:165-171) for a labelled batch: each item carries `image`,
         `intrinsics` and `depth`, an (Hi, Wi) float map of the image's own size (0 = no return).  Keys `loss_dense_depth_lvl_{l}` in
         level order, values 0-d float32 tensors on the model's device; NaN at every level when no pixel of the batch is valid.  Needs
-        DD3D.FCOS3D.DEPTH_HEAD.{LOSS_TYPE, LOSS_WEIGHT} in the config (ValueError otherwise).  Every norm layer uses its running
-        statistics.  The f16x2 range guard acts as in predict_dense_depth.  With `head_grads` the result is (loss dict, grads): the
+        DD3D.FCOS3D.DEPTH_HEAD.{LOSS_TYPE, LOSS_WEIGHT} in the config (ValueError otherwise).  By default every norm layer uses its
+        running statistics.  The f16x2 range guard acts as in predict_dense_depth.  With `head_grads` the result is (loss dict, grads): the
         gradient of the sum of the dict's values with respect to the head's per-level outputs (the reference's `dense_depth_lvl`, after
-        Scale and Offset), {"dense_depth<l>": (B, 1, h_l, w_l) float32 device tensor}; all zeros when no pixel is valid.  There is no
-        backward through the convolutions."""
+        Scale and Offset), {"dense_depth<l>": (B, 1, h_l, w_l) float32 device tensor}; all zeros when no pixel is valid.
+        From `predictor_grads` on the result is (loss dict, grads, param_grads) and the backward goes on through the convolutions with the
+        flags, implications, keys and shapes of DD3D.compute_losses, every deeper flag returning what the shallower one returns bit for
+        bit: `predictor_grads` adds box3d_tower_out<l> to `grads` and to `param_grads` -- keyed by named_parameters() names, float32 of
+        the parameter's shape -- fcos3d_head.dense_depth.<l>.weight ((1, 256, 3, 3)), with USE_SCALE fcos3d_head.scales_depth.<l>.scale
+        and fcos3d_head.offsets_depth.<l>.bias, without it the predictors' .bias; `tower_grads` adds feature<l> and the parameters of
+        fcos3d_head.box3d_tower; `fpn_grads` adds backbone_<name> and the FPN's parameters; `backbone_grads` and `stem_grads` (DLA-34) add
+        backbone_level1, then backbone_level0 and backbone_base_layer, and the bottom-up network's parameters; `vovnet_grads` and
+        `vovnet_stem_grads` (the four covered VoVNet-V2 specs; taken from `**branch`, as `batch_stats` is; any other extra keyword is a TypeError) add
+        backbone_stem_1 and the VoVNet's parameters.  Under `stem_grads` / `vovnet_stem_grads` the keys of `param_grads` are those of
+        named_parameters().  `batch_stats` composes with every flag: a box3d tower whose norm is a trainable BatchNorm2d
+        (DD3D.FCOS3D.NORM: BN) normalises with the batch's statistics per layer, level and channel, and the backward differentiates
+        through them; `get_loss_plan(..., batch_stats=True).tower_batch_stats()` returns them; the model's buffers are never written.
+        What DD3D.compute_losses refuses is refused here in the same words (NotImplementedError: the Bottleneck DLA variants,
+        force_generic_dla, the slim / depthwise VoVNet specs, the reduced arithmetic modes, backbone_grads on a VoVNet, vovnet_grads on a
+        DLA, FE.BACKBONE.NORM / FE.FPN.NORM = BN under batch_stats).  The filter copies the backward reads are snapshots taken when the
+        plan is built; there is no optimiser and no model.train()."""
         from dd3d_amd.engine import relax_arithmetic
+        batch_stats = bool(branch.pop("batch_stats", False))
+        vovnet_stem_grads = bool(branch.pop("vovnet_stem_grads", False))
+        vovnet_grads = bool(branch.pop("vovnet_grads", False)) or vovnet_stem_grads
+        if branch:
+            raise TypeError(f"compute_losses() got an unexpected keyword argument {next(iter(branch))!r}")
         for i, x in enumerate(batched_inputs):
             if "depth" not in x:
                 raise ValueError(f"image {i}: compute_losses needs a 'depth' map in every item of the batch")
         from dd3d_amd.engine.dense_depth_loss import check_depth_maps, dense_depth_loss_config
         dense_depth_loss_config(self.cfg)  # (config and input errors before a plan is built or an image staged)
         check_depth_maps([x["depth"] for x in batched_inputs], [(int(x["image"].shape[-2]), int(x["image"].shape[-1])) for x in batched_inputs])
+        backbone_grads = backbone_grads or stem_grads
+        fpn_grads = fpn_grads or backbone_grads or vovnet_grads
+        tower_grads = tower_grads or fpn_grads
+        flags = dict(vovnet_stem_grads=vovnet_stem_grads, vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads,
+                     fpn_grads=fpn_grads, tower_grads=tower_grads, pred_grads=predictor_grads, head_grads=head_grads)
         while True:
             try:
-                return self._compute_losses(batched_inputs, head_grads)
+                return self._compute_losses(batched_inputs, flags, batch_stats)
             except FloatingPointError as e:
                 if not relax_arithmetic(self, e):
                     raise
 
-    def _compute_losses(self, batched_inputs, head_grads=False):
-        get_plan = (lambda B, H, W: self.get_loss_plan(B, H, W, head_grads=True)) if head_grads else self.get_loss_plan
-        plan, sizes = self._stage(batched_inputs, get_plan)
+    def _compute_losses(self, batched_inputs, flags, batch_stats=False):
+        """One run of the plan of the deepest flag; results are read only behind a passed status check."""
+        plan, sizes = self._stage(batched_inputs, lambda B, H, W: self.get_loss_plan(B, H, W, batch_stats=batch_stats, **_deepest(**flags)))
         plan.stage_depth([x["depth"] for x in batched_inputs], sizes, checked=True)  # (compute_losses has validated the maps)
         plan.run()
         plan.check_status()
-        return (plan.loss_dict(), plan.head_grads()) if head_grads else plan.loss_dict()
+        if not (flags["pred_grads"] or flags["tower_grads"]):
+            return (plan.loss_dict(), plan.head_grads()) if flags["head_grads"] else plan.loss_dict()
+        tens, params = plan.predictor_grads()
+        for name in ("tower_grads", "fpn_grads", "backbone_grads", "stem_grads", "vovnet_grads", "vovnet_stem_grads"):
+            if flags[name]:
+                more_t, more_p = getattr(plan, name)()
+                tens, params = dict(tens, **more_t), dict(params, **more_p)
+        return plan.loss_dict(), dict(plan.head_grads(), **tens), params
 
     def forward(self, batched_inputs):
         raise NotImplementedError()  # the reference's eval-mode forward (dense_depth.py:162-163)
