@@ -285,6 +285,10 @@ class BackboneLowering:
         assert fpn._fuse_type == "sum", "FUSE_TYPE avg is not used by any reference config"
         fused = self.planes_only and self.use_planes  # top-down sum inside the lateral convolution's epilogue (res_mode 3)
         lats = {}
+        if getattr(self, "with_fpn_batch_stats", False):  # LossPlan(fpn_batch_stats=True): the norms on the batch's statistics
+            if not fused:
+                raise NotImplementedError("fpn_batch_stats is built on the fused split-plane FPN (DD3D_PLANES_ONLY=1 and split planes in the plan)")
+            return self._fpn_batch_stats(fpn, feats, p_kind)
         if fused:
             # [ext d2 FPN.forward]: prev = lateral(f) + interpolate(prev, x2, nearest); out = output_conv(prev) -- coarsest level first.  The
             # lateral convolution of a finer level reads the coarser level's SUM out of its split planes (pixel (h/2, w/2)) and adds it in
@@ -348,6 +352,99 @@ class BackboneLowering:
             results[f"p{st}"] = out
         self.fpn_tail_join = 3 if fpn.top_block is not None else None
         return OrderedDict((n, results[n]) for n in fpn._out_features)
+
+    def _fpn_bn_group(self, name, segs, up):
+        """The statistics and the apply of one group of FPN norms behind their raw convolutions (csrc/fpn_bn.hip): `segs`, finest stage
+        first: (stage, norm, raw view, output view); `up`: per segment the index of its coarser segment (the top-down sum) or -1.  Two
+        ops, `<name>.bn_stats` (dd3d_bn_batch_stats, all stages in one call) and `<name>.bn_apply` (dd3d_bn_apply_topdown_split, one
+        launch).  Returns what the backward and the read-out need."""
+        dev, n = self.device, len(segs)
+        Cf = segs[0][3].C
+        assert n <= hip.BN_MAX_SEGS and all(out.np and self.use_planes for *_, out in segs)
+        f = hip.FpnBnArgs()
+        a = f.bn
+        stats = torch.zeros((n, hip.BN_STAT_ROWS, Cf), dtype=torch.float32, device=dev)
+        pixels = [v.B * v.H * v.W for *_, v in segs]
+        rows = hip.bn_slices(pixels)
+        if getattr(self, "fpn_bn_part", None) is None:  # one scratch for both groups, forward and backward: they run in stream order
+            self.fpn_bn_part = torch.zeros(rows * 2 * Cf, dtype=torch.float32, device=dev)
+        assert self.fpn_bn_part.numel() >= rows * 2 * Cf
+        keep = [stats]
+        for s, (st, norm, raw, out) in enumerate(segs):
+            vecs = [self._vec(v) for v in (norm.weight, norm.bias, norm.running_mean, norm.running_var)]
+            keep += vecs
+            a.c[s], a.stats[s], a.N[s] = raw.ptr, stats[s].data_ptr(), pixels[s]
+            a.gamma[s], a.beta[s], a.run_mean[s], a.run_var[s] = (v.data_ptr() for v in vecs)
+            a.y[s] = out.pptr or None
+            f.y32[s] = (out.ptr or None) if out.has_f32 else None  # (DD3D_KEEP_F32=1: the f32 copy beside the planes)
+            f.up[s], f.B[s], f.H[s], f.W[s] = up[s], out.B, out.H, out.W
+            assert float(norm.eps) == float(segs[0][1].eps) and raw.pitch == segs[0][2].pitch and out.pitch == segs[0][3].pitch
+        a.part, a.n_slices, a.status = self.fpn_bn_part.data_ptr(), self.fpn_bn_part.numel() // (2 * Cf), self.status.data_ptr()
+        a.num_segs, a.C, a.c_pitch = n, Cf, segs[0][2].pitch
+        a.math_mode, a.y_pitch, f.y32_pitch = self.math, segs[0][3].pitch, segs[0][3].pitch
+        a.eps, a.momentum, a.plane_scale = float(segs[0][1].eps), hip.BN_MOMENTUM, float(segs[0][3].buf.plane_scale)
+        desc = dict(segs=[dict(stage=st, raw=raw, out=out, norm=norm, up=up[s]) for s, (st, norm, raw, out) in enumerate(segs)], stats=stats)
+        op = CallOp(lambda lib, st_, f=f: hip.check(lib.dd3d_bn_batch_stats(C.byref(f.bn), st_), f"bn_batch_stats {name}"), f"{name}.bn_stats",
+                    dict(desc, kind="bn_batch_stats"))
+        op.keep = keep
+        self.ops.append(op)
+        self.ops.append(CallOp(lambda lib, st_, f=f: hip.check(lib.dd3d_bn_apply_topdown_split(C.byref(f), st_), f"bn_apply_topdown_split {name}"),
+                               f"{name}.bn_apply", dict(desc, kind="bn_apply_topdown_split")))
+        return dict(stages=[st for st, *_ in segs], norms=[norm for _, norm, *_ in segs], raw=[raw for _, _, raw, _ in segs],
+                    stats=[stats[s] for s in range(n)], args=f, ones=self._vec(torch.ones(Cf)))
+
+    def _fpn_batch_stats(self, fpn, feats, p_kind):
+        """[ext d2 FPN.forward] with the lateral and output norms (trainable BatchNorm2d, FE.FPN.NORM: BN) on the batch's statistics, as the
+        reference's train() computes them.  A norm needs its convolution's whole batch before it can be applied, so the top-down sum
+        leaves the lateral convolution's epilogue: every lateral and every output convolution writes its raw f32 result (scale ones, no
+        norm, no residual; `descaled` makes it the exact-f32 convolution), dd3d_bn_batch_stats takes the statistics of all stages in
+        one call and ONE dd3d_bn_apply_topdown_split launch writes the planes -- for the laterals the stored top-down sums
+        t<s> = n_s + up(t<s+1>), every coarser term recomputed from its raw tensor, into the `fpn_lateral<s>` buffers the running-
+        statistics path uses.  A plan with the FPN backward keeps both raw tensors of every stage; any other reuses one per stage."""
+        from dd3d_amd.layers import BatchNorm2d
+        names, stages = list(fpn.in_features), list(fpn.stages)  # finest first
+        Cf = fpn._out_feature_channels[f"p{stages[0]}"]
+        keep = bool(getattr(self, "with_fpn_grads", False))
+        ones, results = torch.ones(Cf), {}
+
+        def raw_seg(conv, vin, raw):
+            assert isinstance(conv.norm, BatchNorm2d), "fpn_batch_stats needs BatchNorm2d norms in the FPN (FE.FPN.NORM: BN)"
+            w, meta = self.pack(dense_filter(conv))
+            shift = conv.bias.detach().float().cpu() if conv.bias is not None else torch.zeros(Cf)
+            return {"in": vin, "out": raw, "w": w, "scale": self._vec(ones), "bias": self._vec(shift)}, meta
+
+        lat_segs, out_segs, lat_raws = [], [], {}
+        for idx in reversed(range(len(names))):  # the laterals read the backbone features alone: all of them first, coarsest first
+            f, st = feats[names[idx]], stages[idx]
+            conv = getattr(fpn, f"fpn_lateral{st}")
+            raw = self.buf(f"fpn_lateral{st}.raw" if keep else f"fpn_raw{st}", f.B, f.H, f.W, Cf).view()
+            lat = self.buf(f"fpn_lateral{st}", f.B, f.H, f.W, Cf, kind="planes").view()
+            seg, meta = raw_seg(conv, f, raw)
+            self.ops.append(ConvOp(self, meta, conv.stride, conv.padding, [seg], relu=False, name=f"fpn_lateral{st}.raw"))
+            lat_segs.insert(0, (st, conv.norm, raw, lat))
+            lat_raws[st] = raw
+        for (st, _, _, lat), (st2, _, _, lat2) in zip(lat_segs, lat_segs[1:]):
+            assert (2 * lat2.H, 2 * lat2.W) == (lat.H, lat.W), "FPN levels whose sizes are not exact halves do not occur on a size-divisible canvas"
+        n = len(lat_segs)
+        self.fpn_bn = OrderedDict()
+        self.fpn_bn["laterals"] = self._fpn_bn_group("fpn_laterals", lat_segs, [s + 1 if s + 1 < n else -1 for s in range(n)])
+        raw_segs, out_meta, bn_segs = [], None, []
+        for st, _, lat_raw, lat in reversed(lat_segs):  # the segment order of the running-statistics launch: coarsest first
+            conv = getattr(fpn, f"fpn_output{st}")
+            assert (conv.stride, conv.padding) == (1, 1)
+            raw = self.buf(f"fpn_output{st}.raw", lat.B, lat.H, lat.W, Cf).view() if keep else lat_raw
+            out = self.buf(f"p{st}", lat.B, lat.H, lat.W, Cf, kind=p_kind).view()
+            seg, meta = raw_seg(conv, lat, raw)
+            assert out_meta is None or {k: meta[k] for k in ("N", "Cin", "KH", "KW", "Kpad")} == {k: out_meta[k] for k in ("N", "Cin", "KH", "KW", "Kpad")}
+            out_meta = meta
+            raw_segs.append(seg)
+            bn_segs.insert(0, (st, conv.norm, raw, out))
+            results[f"p{st}"] = out
+        self.ops.append(ConvOp(self, out_meta, 1, 1, raw_segs, relu=False, name="fpn_outputs.raw"))
+        self.fpn_bn["outputs"] = self._fpn_bn_group("fpn_outputs", bn_segs, [-1] * n)
+        self._top_block(fpn, results, p_kind)
+        self.fpn_tail_join = 3 if fpn.top_block is not None else None
+        return OrderedDict((k, results[k]) for k in fpn._out_features)
 
     def _top_block(self, fpn, results, p_kind):
         """LastLevelP6P7 / LastLevelP6 [ext; built at dla.py:550-557]: p6 = conv(p5), p7 = conv(relu(p6)), on side branch 3."""

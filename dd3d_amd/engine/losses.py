@@ -7,7 +7,7 @@ and the stem's output (csrc/backbone_grads.hip), and last through the stem -- ba
 (csrc/stem_grads.hip); for the VoVNet-V2 backbones, behind the FPN through stage5 .. stage2, stem_3 and stem_2 (csrc/vovnet_grads.hip and
 the wide entry points of csrc/backbone_grads.hip) and last stem_1's filter (dd3d_vovnet_stem_wgrad, csrc/stem_grads.hip).  With
 batch_stats=True the head towers whose norm is a trainable BatchNorm2d use the batch's statistics, forward and backward
-(csrc/tower_bn.hip).  There is no optimiser or model.train().  The chain behind the loss backward (flags, stage builders, read-outs) is the
+(csrc/tower_bn.hip); with fpn_batch_stats=True the FPN's lateral and output norms do (csrc/fpn_bn.hip).  There is no optimiser or model.train().  The chain behind the loss backward (flags, stage builders, read-outs) is the
 mixin ``BackwardStages``: ``LossPlan`` and the dense-depth network's ``DenseDepthLossPlan`` (dense_depth_loss.py) both run it.
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
@@ -717,13 +717,62 @@ class TowerBnGrads(GradCall):
         self.args = a
 
 
-def check_batch_stats(model, B, Hp, Wp):
+class FpnBnGrads(TowerBnGrads):
+    """TowerBnGrads without the mask, for the FPN's norms (csrc/fpn_bn.hip; no ReLU follows them): the segments are the stages, finest
+    first, no stored output is bound.  qp [L, 2, C] holds (d beta, d gamma) of every stage's norm, gc the gradient at its raw convolution."""
+    ENTRIES = (("dd3d_bn_backward_reduce_linear", "bn_backward_reduce_linear"), ("dd3d_bn_backward_apply_linear", "bn_backward_apply_linear"))
+
+    def __init__(self, device, B, level_hw, Cc, raw, g, g_pitch, stats, part, fill=0.0, guard=0):
+        TowerBnGrads.__init__(self, device, B, level_hw, Cc, raw, [(hip.PG_ACT_F32, 0, 0, 1.0)] * len(level_hw), g, g_pitch, stats, part, fill=fill,
+                              guard=guard)
+
+
+def plan_math(model):
+    """The DD3D_MATH_* a plan of `model` will run on (ForwardPlan._trunk's rule), known before the plan exists."""
+    from dd3d_amd.engine.tiling import MATH_NAMES, default_math
+    m = getattr(model, "math", None)
+    return default_math() if m is None else MATH_NAMES[m] if isinstance(m, str) else int(m)
+
+
+def check_fpn_batch_stats(model, B, Hp, Wp):
+    """What LossPlan(fpn_batch_stats=True) refuses before anything is built: an FPN without trainable BatchNorm2d (the flag must not be a
+    silent no-op), a bottom-up network that would need batch statistics too, a stage with one value per channel (in torch's words),
+    widths the kernels do not take, another fuse type, and the lowerings without the fused split-plane FPN."""
+    import math
+    import os
+    cfg, fpn = model.cfg, model.backbone
+    if str(cfg.FE.FPN.NORM) != "BN":
+        raise ValueError(f"fpn_batch_stats needs FE.FPN.NORM = 'BN' (it is {str(cfg.FE.FPN.NORM)!r}): the FPN has no norm that uses batch statistics")
+    if str(cfg.FE.BACKBONE.NORM) == "BN":
+        raise NotImplementedError("fpn_batch_stats covers the FPN; FE.BACKBONE.NORM = 'BN' would need batch statistics in the bottom-up network as well")
+    if fpn._fuse_type != "sum":
+        raise NotImplementedError(f"fpn_batch_stats implements FE.FPN FUSE_TYPE 'sum' (it is {fpn._fuse_type!r})")
+    Cf = int(getattr(fpn, f"fpn_output{fpn.stages[0]}").out_channels)
+    if Cf % 32 or Cf > hip.BN_MAX_C:
+        raise NotImplementedError(f"fpn_batch_stats needs FE.FPN.OUT_CHANNELS to be a multiple of 32 up to {hip.BN_MAX_C} (it is {Cf})")
+    for s in fpn.stages:
+        h, w = math.ceil(Hp / 2**s), math.ceil(Wp / 2**s)
+        if B * h * w < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size [{B}, {Cf}, {h}, {w}] "
+                             f"(FPN stage {s} on a {Hp} x {Wp} canvas)")
+    mode = plan_math(model)
+    if mode in (hip.MATH_BF16X2, hip.MATH_BF16):
+        name = {hip.MATH_BF16X2: "bf16x2", hip.MATH_BF16: "bf16"}[mode]
+        raise NotImplementedError(f"fpn_batch_stats stores f16x2 or bf16x3 planes; the arithmetic mode {name!r} has no apply")
+    for on, what in ((mode == hip.MATH_F32, "DD3D_MATH=f32"), (mode == hip.MATH_BF16X3 and os.environ.get("DD3D_PLANES", "1") == "0", "DD3D_PLANES=0"),
+                     (os.environ.get("DD3D_PLANES_ONLY", "1") == "0", "DD3D_PLANES_ONLY=0")):
+        if on:
+            raise NotImplementedError(f"fpn_batch_stats is built on the fused split-plane FPN; {what} selects the round-3 FPN lowering, which has no "
+                                      "batch-statistics form (separate top-down launches on f32 laterals)")
+
+
+def check_batch_stats(model, B, Hp, Wp, fpn_covered=False):
     """What LossPlan(batch_stats=True) refuses before anything is built: a level with one value per channel (the reference raises there
-    too, in torch's words) and trunk norms that would need batch statistics as well."""
+    too, in torch's words) and trunk norms that would need batch statistics as well (`fpn_covered`: fpn_batch_stats=True gives the FPN's)."""
     import math
     cfg = model.cfg
     for key, node in (("FE.BACKBONE.NORM", cfg.FE.BACKBONE), ("FE.FPN.NORM", cfg.FE.FPN)):
-        if str(node.NORM) == "BN":
+        if str(node.NORM) == "BN" and not (fpn_covered and key == "FE.FPN.NORM"):
             raise NotImplementedError(f"batch_stats covers the head towers; {key} = 'BN' would need batch statistics in the trunk as well")
     for s in model.backbone_output_shape:
         h, w = math.ceil(Hp / s.stride), math.ceil(Wp / s.stride)
@@ -886,7 +935,9 @@ def conv_param_grads(named, lay, conv, norm, dw, scale, q, r):
     params = {}
     k, cin = lay.ksize, int(conv.weight.shape[1])
     if id(conv.weight) in named:
-        params[named[id(conv.weight)]] = dw.view(lay.Cout, k, k, lay.Cin)[..., :cin].permute(0, 3, 1, 2).contiguous()
+        # (a copy even where the permuted view is contiguous already -- a 1 x 1 filter over all of the buffer's channels: the read-outs
+        # return copies, never the plan's own memory, which the next run overwrites)
+        params[named[id(conv.weight)]] = dw.view(lay.Cout, k, k, lay.Cin)[..., :cin].permute(0, 3, 1, 2).clone(memory_format=torch.contiguous_format)
     got = norm_param_grads(conv, norm, scale, q, r)
     for key, p in (("norm.weight", getattr(norm, "weight", None)), ("norm.bias", getattr(norm, "bias", None)), ("bias", conv.bias)):
         if key in got and id(p) in named:
@@ -1086,14 +1137,19 @@ def fpn_slab_words(B, fpn, acts):
     return max(sl * Cf * kk for sl, kk in n), max(sl * Cf for sl, _ in n)
 
 
-def fpn_backward(device, B, fpn, G, acts, vec, slab=None, fill=0.0, guard=0):
+def fpn_backward(device, B, fpn, G, acts, vec, slab=None, fill=0.0, guard=0, bn=None):
     """The calls of the FPN backward in their order (include/dd3d_hip.h states the mathematics): the top block (P7, then P6) down to D
     of the coarsest stage; the output convolutions (all weight gradients in one call, a filter per level; the input gradients finest
     stage first, each adding the 2x2 sums of the finer stage's: the transposed top-down path); the laterals, coarsest stage first.
 
     `G`: {p<s>: [B, h, w, Cf] gradient at every FPN output}; `acts`: {t<s> (stored top-down sum), p<s> (the coarsest stage's output and
     p6), backbone feature name: ((mode, address, pitch, plane scale), H, W, C)} as stored; `vec`: host vector -> device.  Returns
-    ({key: FpnConvGrads}, {feature name: (gradient [B, h, w, C], real channels)}); a layer's `conv` is its module (`outputs`: a list)."""
+    ({key: FpnConvGrads}, {feature name: (gradient [B, h, w, C], real channels)}); a layer's `conv` is its module (`outputs`: a list).
+
+    `bn` (fpn_batch_stats): {"outputs" / "laterals": dict(raw=[(address, pitch)], stats=[tensor], part=scratch, ones=[C]) per stage, finest
+    first}.  Then the norms' backward runs in front of the convolutions': one FpnBnGrads over all stages on D and the output raws before
+    `outputs`, one on T (the transposed top-down sums already added) and the lateral raws before the laterals; the convolution calls run
+    on g := G_c with scale ones.  A convolution layer's `bn` is its FpnBnGrads (else None), `bn_index` its stages' rows of bn.qp."""
     from dd3d_amd.layers import fold_norm
     if fpn._fuse_type != "sum":
         raise NotImplementedError("FPN gradients implement FUSE_TYPE 'sum' (as the forward)")
@@ -1123,17 +1179,28 @@ def fpn_backward(device, B, fpn, G, acts, vec, slab=None, fill=0.0, guard=0):
         D_top = lay.da[0]
     D = [G[f"p{s}"] for s in stages[:-1]] + [D_top]
     convs = [getattr(fpn, f"fpn_output{s}") for s in stages]
-    lay = FpnConvGrads(device, B, [hw(f"t{s}") for s in stages], Cf, Cf, 3, 1, [acts[f"t{s}"][0] for s in stages], D, Cf, [filt(c, Cf) for c in convs],
-                       [scale_of(c) for c in convs], pool=[None] + ["prev"] * (len(stages) - 1), **common)
-    lay.conv = convs
+    stage_hw = [hw(f"t{s}") for s in stages]
+
+    def norm_backward(rec, g):
+        return FpnBnGrads(device, B, stage_hw, Cf, rec["raw"], g, Cf, rec["stats"], rec["part"], fill=fill, guard=guard)
+
+    out_bn = norm_backward(bn["outputs"], D) if bn is not None else None
+    lay = FpnConvGrads(device, B, stage_hw, Cf, Cf, 3, 1, [acts[f"t{s}"][0] for s in stages], D if out_bn is None else out_bn.gc, Cf,
+                       [filt(c, Cf) for c in convs], [scale_of(c) for c in convs] if out_bn is None else [bn["outputs"]["ones"]] * len(stages),
+                       pool=[None] + ["prev"] * (len(stages) - 1), **common)
+    lay.conv, lay.bn, lay.bn_index = convs, out_bn, list(range(len(stages)))
     layers["outputs"] = lay
     T = lay.da
+    lat_bn = norm_backward(bn["laterals"], T) if bn is not None else None
+    if lat_bn is not None:
+        T = lat_bn.gc
     backbone = OrderedDict()
     for idx in reversed(range(len(stages))):
         n, conv = names[idx], getattr(fpn, f"fpn_lateral{stages[idx]}")
         cin = acts[n][3]
-        lay = FpnConvGrads(device, B, [hw(n)], cin, Cf, 1, 1, [acts[n][0]], [T[idx]], Cf, [filt(conv, cin)], [scale_of(conv)], **common)
-        lay.conv = conv
+        lay = FpnConvGrads(device, B, [hw(n)], cin, Cf, 1, 1, [acts[n][0]], [T[idx]], Cf, [filt(conv, cin)],
+                           [scale_of(conv) if lat_bn is None else bn["laterals"]["ones"]], **common)
+        lay.conv, lay.bn, lay.bn_index = conv, lat_bn, [idx]
         layers[f"lateral{stages[idx]}"] = lay
         backbone[n] = (lay.da[0], int(conv.weight.shape[1]))
     return layers, backbone
@@ -1145,8 +1212,18 @@ def fpn_param_grads(named, layers):
     params = {}
     for lay in layers.values():
         convs = lay.conv if isinstance(lay.conv, list) else [lay.conv]
+        bn = getattr(lay, "bn", None)
         for l, conv in enumerate(convs):
-            params.update(conv_param_grads(named, lay, conv, getattr(conv, "norm", None), lay.dw[l], lay.keep[2][l], lay.q[l], lay.r[l]))
+            if bn is None:
+                params.update(conv_param_grads(named, lay, conv, getattr(conv, "norm", None), lay.dw[l], lay.keep[2][l], lay.q[l], lay.r[l]))
+                continue
+            # batch statistics: d gamma = p, d beta = q of the norm's backward; the GEMM call's own q / r are by-products (q: the sum of G_c,
+            # a conv bias' gradient -- zero up to rounding, the norm removes the mean)
+            params.update(conv_param_grads(named, lay, conv, None, lay.dw[l], lay.keep[2][l], lay.q[l], lay.r[l]))
+            qp = bn.qp[lay.bn_index[l]]
+            for p, v in ((conv.norm.weight, qp[1]), (conv.norm.bias, qp[0])):
+                if id(p) in named:
+                    params[named[id(p)]] = v.clone()
     return params
 
 
@@ -1186,11 +1263,16 @@ class BackwardStages:
     A plan mixes this in beside its forward plan; what it must provide: `tower_info`, `tower_out`, `pred_info`, `tower_bn` / `bn_part` as
     ForwardPlan._heads records them, `_pred_group_table` (what the predictor groups bind), and `grads` handled by its own loss backward."""
     def _chain_flags(self, model, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
-                     stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False):
+                     stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False, fpn_batch_stats=False):
         """The flags of the chain, each implying the shallower ones, and what they refuse before anything is built or launched."""
         self.batch_stats = bool(batch_stats)
-        if self.batch_stats:  # before anything is built or launched
+        self.with_fpn_batch_stats = bool(fpn_batch_stats)  # (`fpn_batch_stats` itself is the read-out method; read by the trunk: _fpn)
+        if self.batch_stats and not self.with_fpn_batch_stats:  # before anything is built or launched
             check_batch_stats(model, B, Hp, Wp)
+        if self.with_fpn_batch_stats:
+            check_fpn_batch_stats(model, B, Hp, Wp)
+            if self.batch_stats:  # (FE.FPN.NORM = BN is what the other flag covers)
+                check_batch_stats(model, B, Hp, Wp, fpn_covered=True)
         self.with_vovnet_stem_grads = bool(vovnet_stem_grads)  # (`vovnet_stem_grads` itself is the read-out method)
         self.with_vovnet_grads = bool(vovnet_grads) or self.with_vovnet_stem_grads  # (`vovnet_grads` itself is the read-out method)
         if self.with_vovnet_grads:  # before anything is built or launched
@@ -1436,8 +1518,23 @@ class BackwardStages:
             G[name] = self.feature_grads[selected.index(name)] if name in selected else torch.zeros((B, v.H, v.W, Cf), dtype=torch.float32, device=dev)
             assert tuple(G[name].shape) == (B, v.H, v.W, Cf)
         self._grow_slab(*fpn_slab_words(B, fpn, acts), budget=False)
-        self.fpn_layers, self.backbone_feature_grads = fpn_backward(dev, B, fpn, G, acts, self._vec, slab=self.tower_slab)
-        self._append_calls("fpn_grads", self.fpn_layers)
+        bn = None
+        if self.with_fpn_batch_stats:  # the norms' backward reads every stage's stored raw convolution outputs and statistics
+            bn = {k: dict(raw=[(v.ptr, v.pitch) for v in rec["raw"]], stats=list(rec["stats"]), part=self.fpn_bn_part, ones=rec["ones"])
+                  for k, rec in self.fpn_bn.items()}
+            self.fpn_bn_reads = self._check_reads("FPN norm", [v for rec in self.fpn_bn.values() for v in rec["raw"]])
+        self.fpn_layers, self.backbone_feature_grads = fpn_backward(dev, B, fpn, G, acts, self._vec, slab=self.tower_slab, bn=bn)
+        if bn is None:
+            self._append_calls("fpn_grads", self.fpn_layers)
+        else:  # each norm's call in front of the first convolution call that reads its G_c
+            self.fpn_bn_layers = OrderedDict()
+            for key, lay in self.fpn_layers.items():
+                norm = getattr(lay, "bn", None)
+                if norm is not None and all(norm is not b for b in self.fpn_bn_layers.values()):
+                    name = "outputs" if key == "outputs" else "laterals"
+                    self.fpn_bn_layers[name] = norm
+                    self.ops.append(CallOp(lambda lib, st, b=norm: b.launch(lib, st), f"fpn_bn_grads.{name}", dict(kind="fpn_bn_grads", layer=name)))
+                self._append_calls("fpn_grads", {key: lay})
         self.fpn_reads, self.fpn_pinned = self._check_reads("FPN", [v for _, v in reads]), []  # (nothing needs pinning beyond the check)
 
     def fpn_grads(self):
@@ -1610,14 +1707,32 @@ class BackwardStages:
         return out
 
 
+    def fpn_batch_stats(self):
+        """The FPN norms' batch statistics of the last run, copies keyed by the state-dict names of `backbone.fpn_lateral<s>.norm` and
+        `backbone.fpn_output<s>.norm`: `.running_mean` / `.running_var` as one training step would leave them, `.batch_mean` /
+        `.batch_var` the batch's mean and biased variance (tower_batch_stats' conventions).  The model's own buffers are never written."""
+        if not self.with_fpn_batch_stats:
+            raise self._built_without("fpn_batch_stats")
+        names = {id(b): k for k, b in self.model.named_buffers()}
+        out = {}
+        for rec in self.fpn_bn.values():
+            for norm, st in zip(rec["norms"], rec["stats"]):
+                mean_name, var_name = names[id(norm.running_mean)], names[id(norm.running_var)]
+                out[mean_name], out[var_name] = st[hip.BN_ROW_RUN_MEAN].clone(), st[hip.BN_ROW_RUN_VAR].clone()
+                stem = mean_name[:-len("running_mean")]
+                out[stem + "batch_mean"], out[stem + "batch_var"] = st[hip.BN_ROW_MU].clone(), st[hip.BN_ROW_VAR].clone()
+        return out
+
+
 class LossPlan(BackwardStages, ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
     def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
-                 fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False):
+                 fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False,
+                 fpn_batch_stats=False):
         self._chain_flags(model, B, Hp, Wp, grads=grads, pred_grads=pred_grads, tower_grads=tower_grads, fpn_grads=fpn_grads,
                           backbone_grads=backbone_grads, stem_grads=stem_grads, vovnet_grads=vovnet_grads, batch_stats=batch_stats,
-                          vovnet_stem_grads=vovnet_stem_grads)
+                          vovnet_stem_grads=vovnet_stem_grads, fpn_batch_stats=fpn_batch_stats)
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
         check_loss_config(model.cfg)
         from dd3d_amd.engine.tiling import default_tile_policy

@@ -425,6 +425,14 @@ class TowerBnArgs(C.Structure):
     ]
 
 
+class FpnBnArgs(C.Structure):
+    """`dd3d_fpn_bn_args`."""
+    _fields_ = [
+        ("bn", TowerBnArgs), ("y32", C.c_void_p * BN_MAX_SEGS), ("up", C.c_int32 * BN_MAX_SEGS), ("B", C.c_int32 * BN_MAX_SEGS),
+        ("H", C.c_int32 * BN_MAX_SEGS), ("W", C.c_int32 * BN_MAX_SEGS), ("y32_pitch", C.c_int32), ("reserved", C.c_int32)
+    ]
+
+
 def bn_slices(pixels):
     """Rows of `part` one dd3d_bn_batch_stats / dd3d_bn_backward_reduce call needs for segments of `pixels` pixels each (the rule of
     dd3d_bn_slices, for plans built without a device)."""
@@ -447,7 +455,8 @@ EXPORTS = [
     "dd3d_vovnet_stem_wgrad", "dd3d_vovnet_stem_grad_slices",
     "dd3d_vovnet_conv_wgrad", "dd3d_vovnet_conv_dgrad", "dd3d_vovnet_conv_grad_slices", "dd3d_vovnet_add", "dd3d_ese_backward", "dd3d_maxpool3x3s2_ceil_backward",
     "dd3d_vovnet_grad_layout",
-    "dd3d_bn_batch_stats", "dd3d_bn_apply_relu_split", "dd3d_bn_backward_reduce", "dd3d_bn_backward_apply", "dd3d_bn_slices", "dd3d_tower_bn_layout"
+    "dd3d_bn_batch_stats", "dd3d_bn_apply_relu_split", "dd3d_bn_backward_reduce", "dd3d_bn_backward_apply", "dd3d_bn_slices", "dd3d_tower_bn_layout",
+    "dd3d_bn_apply_topdown_split", "dd3d_bn_backward_reduce_linear", "dd3d_bn_backward_apply_linear", "dd3d_fpn_bn_layout"
 ]
 
 
@@ -569,6 +578,10 @@ def lib():
     L.dd3d_bn_slices.argtypes = [C.POINTER(TowerBnArgs)]
     L.dd3d_bn_slices.restype = C.c_int64
     L.dd3d_tower_bn_layout.argtypes = [C.c_void_p, C.c_int32]
+    L.dd3d_bn_apply_topdown_split.argtypes = [C.POINTER(FpnBnArgs), C.c_void_p]
+    for name in ("dd3d_bn_backward_reduce_linear", "dd3d_bn_backward_apply_linear"):
+        getattr(L, name).argtypes = [C.POINTER(TowerBnArgs), C.c_void_p]
+    L.dd3d_fpn_bn_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

@@ -126,7 +126,7 @@ class DD3D(nn.Module):
         return plan
 
     def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False, stem_grads=False,
-                      vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False):
+                      vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False, fpn_batch_stats=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
         `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
         backward behind it as well (parameter and tower-output gradients; implies `grads`); `tower_grads`: the plan that goes on through
@@ -140,13 +140,16 @@ class DD3D(nn.Module):
         through stem_1 (its parameter gradients; the image has no gradient; implies `vovnet_grads`, and raises for whatever that raises for);
         `batch_stats`: the head towers whose norm is
         a trainable BatchNorm2d use the batch's statistics, as the reference's train() does (composes with every level above; a plan of
-        its own beside the running-statistics one)."""
+        its own beside the running-statistics one); `fpn_batch_stats`: the FPN's lateral and output norms (FE.FPN.NORM: BN) use the batch's
+        statistics (composes with every level above and with `batch_stats`; one more plan and cache key of its own)."""
         from dd3d_amd.engine.losses import LossPlan
         level = _deepest(vovnet_stem_grads=vovnet_stem_grads, vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads,
                          fpn_grads=fpn_grads, tower_grads=tower_grads, pred_grads=pred_grads, grads=grads)
         key = ("losses", B, Hp, Wp, self.math, self.act_scale, getattr(self, "tile_policy", None)) + tuple(level)
         if batch_stats:
             key, level = key + ("batch_stats", ), dict(level, batch_stats=True)
+        if fpn_batch_stats:
+            key, level = key + ("fpn_batch_stats", ), dict(level, fpn_batch_stats=True)
         plan = self._plans.pop(key, None)
         if plan is None:
             plan = LossPlan(self, B, Hp, Wp, **level)
@@ -312,7 +315,7 @@ class DD3D(nn.Module):
     # ------------------------------------------------------------------ training losses (gradients: head maps and the predictor layer)
     @torch.no_grad()
     def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
-                       stem_grads=False, batch_stats=False, **branch):
+                       stem_grads=False, batch_stats=False, fpn_batch_stats=False, **branch):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
@@ -362,11 +365,24 @@ class DD3D(nn.Module):
         `get_loss_plan(..., batch_stats=True)`) returns the running statistics the step would leave and the batch's own, and the
         model's buffers are never written.  A level with one value per channel (one 64 x 128 image: P7 is 1 x 1) raises ValueError in
         torch's words; FE.BACKBONE.NORM / FE.FPN.NORM = BN raise NotImplementedError naming the key.
+        With `fpn_batch_stats` (it composes with every flag above, `batch_stats` included) the FPN's trainable
+        BatchNorm2d norms -- fpn_lateral<s>.norm and fpn_output<s>.norm under FE.FPN.NORM: BN, eps 1e-5 -- normalise with the mean and
+        biased variance of their own convolution's output over the B * h_s * w_s pixels of the padded canvas, the top-down sum adds the
+        normalised laterals in float32, and the backward goes through both statistics (csrc/fpn_bn.hip); the top block is unchanged.
+        Keys and shapes of every result stay; backbone.fpn_lateral<s>.norm.weight / .bias and the fpn_output<s> pair in `param_grads`
+        are the norm backward's sums.  `plan.fpn_batch_stats()` (the plan of `get_loss_plan(..., fpn_batch_stats=True)`) returns the
+        running statistics the step would leave and the batch's own; the model's buffers are never written.  It is the reference's
+        train() forward of an FPN on a frozen bottom-up network: FE.BACKBONE.NORM = BN still raises NotImplementedError naming the key
+        (the DLA / VoVNet network would need batch statistics too).  FE.FPN.NORM other than BN raises ValueError naming the key (the
+        flag is never a silent no-op), a stage with one value per channel ValueError in torch's words; FE.FPN.OUT_CHANNELS not a
+        multiple of 32 or above 256, FUSE_TYPE avg, DD3D_PLANES=0, DD3D_PLANES_ONLY=0, DD3D_MATH=f32 and the reduced arithmetic modes
+        raise NotImplementedError.  `batch_stats=True` alone keeps refusing FE.FPN.NORM = BN.
         The filter copies the backward reads are snapshots taken when the plan is built; there is no optimiser and no model.train().  V2-99, the Bottleneck DLA variants, force_generic_dla and the reduced arithmetic modes raise
         NotImplementedError."""
         from dd3d_amd.engine import relax_arithmetic
         vovnet_stem_grads = bool(branch.pop("vovnet_stem_grads", False))
         vovnet_grads = bool(branch.pop("vovnet_grads", False)) or vovnet_stem_grads
+        norms = dict(batch_stats=batch_stats, fpn_batch_stats=True) if fpn_batch_stats else dict(batch_stats=batch_stats)
         if branch:
             raise TypeError(f"compute_losses() got an unexpected keyword argument {next(iter(branch))!r}")
         gt = [x["instances"] for x in batched_inputs]
@@ -376,7 +392,7 @@ class DD3D(nn.Module):
             tower_grads = tower_grads or fpn_grads
             level = _deepest(vovnet_stem_grads=vovnet_stem_grads, vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads,
                              fpn_grads=fpn_grads, tower_grads=tower_grads, pred_grads=predictor_grads, grads=head_grads)
-            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), batch_stats=batch_stats, **level)
+            plan = self.get_loss_plan(*self.canvas_size(batched_inputs), **norms, **level)
             plan.stage_gt(gt)
             self.stage_inputs(batched_inputs, plan=plan)  # (its flush ships the GT too)
             plan.run()

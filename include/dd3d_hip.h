@@ -1337,6 +1337,47 @@ int dd3d_bn_backward_apply(const dd3d_tower_bn_args* args, void* stream);
 int64_t dd3d_bn_slices(const dd3d_tower_bn_args* args);
 int dd3d_tower_bn_layout(int64_t* out, int32_t n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batch-statistics BatchNorm of the FPN's lateral and output convolutions (csrc/fpn_bn.hip): nn.BatchNorm2d in train() behind a
+ * convolution WITHOUT a ReLU, and, for the laterals, detectron2's top-down path prev = lateral + interpolate(prev, x2, nearest).  A
+ * SEGMENT is one pyramid stage: N = B * H * W pixels of the padded canvas.  The statistics are dd3d_bn_batch_stats' (above), one call
+ * over all stages.  With n_l(b, y, x) = fmaf(c_l - mu_l, s_l, beta_l) of segment l at its own pixel:
+ *   unlinked segment (up[l] = -1):   y_l = n_l
+ *   linked chain l -> u1 = up[l] -> u2 = up[u1] -> ... -> uk (up[uk] = -1), every link an exact halving of H and W:
+ *     y_l(b, y, x) = (...((n_uk(b, y >> k, x >> k) + n_u(k-1)(b, y >> (k-1), x >> (k-1))) + ...) + n_u1(b, y >> 1, x >> 1)) + n_l(b, y, x)
+ *   the COARSEST term first, every coarser term recomputed from that segment's raw c: the float32 value of the reference's
+ *   recurrence (float addition commutes: n4 + up(n5) == n5 + n4), in one launch, with no dependence between segments and without
+ *   reading a rounded stored sum.  No ReLU: negative values are stored.
+ * and with G the gradient at y_l's norm output (for a lateral: at the stored sum, which passes it on unchanged):
+ *   q = sum(G)   p = sum(G * xhat)   G_c = s * (G - q / N - xhat * p / N)            xhat = (c - mu) * rstd
+ *   -- dd3d_bn_backward_reduce / _apply (above) without the mask: same slices, same order of every sum, same scratch rows, and the
+ *   bits those return for a stored y of ones; y, y_mode, y_pitch and plane_scale are not read.
+ * dd3d_bn_apply_topdown_split (one launch, thread = (pixel, 8 channels), 16-byte loads and stores, one writer per word): y of every
+ *   segment from bn.c, bn.beta and bn.stats rows MU, S, stored as dd3d_bn_apply_relu_split stores: split planes of bn.math_mode in
+ *   bn.y (DD3D_MATH_F16X2: halves of value * plane_scale; |value * plane_scale| > 65504 or a NaN ORs DD3D_STATUS_F16_OVERFLOW into
+ *   bn.status) or, DD3D_MATH_F32, f32 NHWC of pitch bn.y_pitch.  y32[l] (optional, split-plane modes): an f32 NHWC copy, pitch y32_pitch.
+ *   Segments are ordered finest to coarsest within a chain: up[l] is -1 or an index above l.
+ * dd3d_bn_backward_reduce_linear (two launches): qp; reads c, g, stats rows MU, RSTD.
+ * dd3d_bn_backward_apply_linear (one launch): gc; reads c, g, qp and stats rows MU, RSTD, S.
+ * All are safe under stream capture and write nothing beyond the outputs named and the scratch rows in use.  No float atomics.
+ * dd3d_fpn_bn_layout: sizeof and field offsets (layout check of the bindings; host only).
+ * Rejected (-1, dd3d_last_error starts with the entry point's name): what the tower entry points reject, and for the apply a segment
+ *   whose N is not B * H * W, a link that is not above its segment or below num_segs, a linked segment that is not exactly twice its
+ *   coarser one in H and W or differs in B, a y32 pitch that is not a multiple of 4 or below C.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct dd3d_fpn_bn_args {     /* host memory; every pointer is device memory */
+  dd3d_tower_bn_args bn;              /* c, beta, stats, y, status, N, num_segs, C, c_pitch, math_mode, y_pitch, plane_scale */
+  float* y32[DD3D_BN_MAX_SEGS];       /* optional f32 copy of y: [N][y32_pitch] */
+  int32_t up[DD3D_BN_MAX_SEGS];       /* the segment's coarser segment, or -1 */
+  int32_t B[DD3D_BN_MAX_SEGS], H[DD3D_BN_MAX_SEGS], W[DD3D_BN_MAX_SEGS];
+  int32_t y32_pitch;
+  int32_t reserved;                   /* 0; ignored */
+} dd3d_fpn_bn_args;
+int dd3d_bn_apply_topdown_split(const dd3d_fpn_bn_args* args, void* stream);
+int dd3d_bn_backward_reduce_linear(const dd3d_tower_bn_args* args, void* stream);
+int dd3d_bn_backward_apply_linear(const dd3d_tower_bn_args* args, void* stream);
+int dd3d_fpn_bn_layout(int64_t* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
