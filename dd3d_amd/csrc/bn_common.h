@@ -1,5 +1,5 @@
 // What the batch-statistics BatchNorm translation units share (tower_bn.hip: the head towers, behind a ReLU; fpn_bn.hip: the FPN,
-// without one): the slice / finish reductions, the backward apply, the split-plane store of an 8-channel group and the argument
+// without one; backbone_bn.hip: the DLA-34 bottom-up network, widths 16 .. 512 -- `wide` in the checks): the slice / finish reductions, the backward apply, the split-plane store of an 8-channel group and the argument
 // checks.  MASK = true gates the gradient with the sign of the stored output y; MASK = false reads no y at all and computes what
 // MASK = true computes for a y of ones, bit for bit.  include/dd3d_hip.h states the mathematics and the order of every sum.
 #pragma once
@@ -63,14 +63,15 @@ __global__ __launch_bounds__(BN_T) void bn_slice_kernel(const BnK k) {
   const int slice = blockIdx.x;
   int s = 0;
   while (s + 1 < a.num_segs && slice >= k.slice_off[s + 1]) ++s;
-  const int C = a.C, CQ = C >> 2, P = BN_T / CQ;
+  // a block takes min(C, 256) channels: C <= 256 is one chunk (blockIdx.y = 0), the backbone's C = 512 two (backbone_bn.hip)
+  const int C = a.C, CB = C < BN_T ? C : BN_T, ch0 = (int)blockIdx.y * CB, CQ = CB >> 2, P = BN_T / CQ;
   const int tid = threadIdx.x, cq = tid % CQ, lane = tid / CQ;
   const int N = a.N[s];
   const int p0 = (slice - k.slice_off[s]) * DD3D_BN_SLICE;
   const int p1 = min(p0 + DD3D_BN_SLICE, N);
   if (lane < P) {
-    const float* c = a.c[s] + cq * 4;
-    const float* st = a.stats[s] + cq * 4;
+    const float* c = a.c[s] + ch0 + cq * 4;
+    const float* st = a.stats[s] + ch0 + cq * 4;
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f}, mu = acc0, rstd = acc0;
     if constexpr (KIND >= 1) mu = *reinterpret_cast<const f32x4*>(st + DD3D_BN_ROW_MU * C);
     if constexpr (KIND == 2) rstd = *reinterpret_cast<const f32x4*>(st + DD3D_BN_ROW_RSTD * C);
@@ -86,11 +87,11 @@ __global__ __launch_bounds__(BN_T) void bn_slice_kernel(const BnK k) {
           acc0[e] = fmaf(d, d, acc0[e]);
         }
       } else {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(a.g[s] + (long)p * a.g_pitch + cq * 4);
+        const f32x4 g = *reinterpret_cast<const f32x4*>(a.g[s] + (long)p * a.g_pitch + ch0 + cq * 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float gh = g[e];
-          if constexpr (MASK) gh = load_act_any(a.y_mode, a.y[s], N, p, cq * 4 + e, a.y_pitch, inv) > 0.f ? gh : 0.f;
+          if constexpr (MASK) gh = load_act_any(a.y_mode, a.y[s], N, p, ch0 + cq * 4 + e, a.y_pitch, inv) > 0.f ? gh : 0.f;
           acc0[e] += gh;
           acc1[e] = fmaf(gh, (v[e] - mu[e]) * rstd[e], acc1[e]);
         }
@@ -98,17 +99,17 @@ __global__ __launch_bounds__(BN_T) void bn_slice_kernel(const BnK k) {
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      red[0][lane * C + cq * 4 + e] = acc0[e];
-      if constexpr (KIND == 2) red[1][lane * C + cq * 4 + e] = acc1[e];
+      red[0][lane * CB + cq * 4 + e] = acc0[e];
+      if constexpr (KIND == 2) red[1][lane * CB + cq * 4 + e] = acc1[e];
     }
   }
   __syncthreads();
-  if (tid < C) {
-    float* row = a.part + (long)slice * 2 * C;
+  if (tid < CB) {
+    float* row = a.part + (long)slice * 2 * C + ch0;
     float t0 = 0.f, t1 = 0.f;
     for (int j = 0; j < P; ++j) {
-      t0 += red[0][j * C + tid];
-      if constexpr (KIND == 2) t1 += red[1][j * C + tid];
+      t0 += red[0][j * CB + tid];
+      if constexpr (KIND == 2) t1 += red[1][j * CB + tid];
     }
     if constexpr (KIND == 1) {
       row[C + tid] = t0;
@@ -124,7 +125,9 @@ __global__ __launch_bounds__(BN_T) void bn_finish_kernel(const BnK k) {
   __shared__ float red[2][BN_LANES][32];
   const dd3d_tower_bn_args& a = k.a;
   const int s = blockIdx.y, C = a.C;
-  const int tid = threadIdx.x, ci = tid & 31, lane = tid >> 5, c = blockIdx.x * 32 + ci;
+  const int tid = threadIdx.x, ci = tid & 31, lane = tid >> 5;
+  const bool live = (int)blockIdx.x * 32 + ci < C;  // (C = 16, backbone_bn.hip: the upper half of the block reads channel 0 and stores nothing)
+  const int c = live ? blockIdx.x * 32 + ci : 0;
   const int sl0 = k.slice_off[s], sl1 = k.slice_off[s + 1];
   float t0 = 0.f, t1 = 0.f;
   // four of the lane's rows are fetched before they are added, in the lane's order (a row past the end adds an exact zero)
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(BN_T) void bn_finish_kernel(const BnK k) {
   red[0][lane][ci] = t0;
   red[1][lane][ci] = t1;
   __syncthreads();
-  if (tid >= 32) return;
+  if (tid >= 32 || !live) return;
   t0 = t1 = 0.f;
   for (int j = 0; j < BN_LANES; ++j) t0 += red[0][j][ci], t1 += red[1][j][ci];
   const float n = (float)a.N[s];
@@ -196,10 +199,20 @@ __global__ __launch_bounds__(BN_T) void bn_dapply_kernel(const BnK k) {
   }
 }
 
-static int check_bn_shape(const dd3d_tower_bn_args* a, const char* who) {
+// `wide`: the widths of backbone_bn.hip (DD3D_BBN_*) in place of the towers' / the FPN's
+static bool bn_width_ok(int C, bool wide) {
+  if (!wide) return C >= 32 && C % 32 == 0 && C <= DD3D_BN_MAX_C;
+  return C == DD3D_BBN_MIN_C || (C >= 32 && C % 32 == 0 && C <= BN_T) || (C % BN_T == 0 && C > 0 && C <= DD3D_BBN_MAX_C);
+}
+
+static int check_bn_shape(const dd3d_tower_bn_args* a, const char* who, bool wide = false) {
   DD3D_REQUIRE(a != nullptr, "%s: null args", who);
   DD3D_REQUIRE(a->num_segs >= 1 && a->num_segs <= DD3D_BN_MAX_SEGS, "%s: %d segments (1 .. %d)", who, a->num_segs, DD3D_BN_MAX_SEGS);
-  DD3D_REQUIRE(a->C >= 32 && a->C % 32 == 0 && a->C <= DD3D_BN_MAX_C, "%s: C = %d is not a multiple of 32 up to %d", who, a->C, DD3D_BN_MAX_C);
+  if (wide)
+    DD3D_REQUIRE(bn_width_ok(a->C, true), "%s: C = %d is not %d, a multiple of 32 up to %d or a multiple of %d up to %d", who, a->C, DD3D_BBN_MIN_C, BN_T, BN_T,
+                 DD3D_BBN_MAX_C);
+  else
+    DD3D_REQUIRE(bn_width_ok(a->C, false), "%s: C = %d is not a multiple of 32 up to %d", who, a->C, DD3D_BN_MAX_C);
   long rows = 0;
   for (int s = 0; s < a->num_segs; ++s) {
     DD3D_REQUIRE(a->N[s] >= 2, "%s: segment %d has N = %d (batch statistics need more than 1 value per channel)", who, s, a->N[s]);
@@ -210,8 +223,8 @@ static int check_bn_shape(const dd3d_tower_bn_args* a, const char* who) {
 }
 
 // `need`: bit 0 g / qp, bit 1 gc, bit 2 the stored y as a DD3D_PG_ACT_* storage, bit 3 the statistics' inputs, bit 4 the scratch rows
-static int check_bn_args(const dd3d_tower_bn_args* a, const char* who, int need) {
-  const int rc = check_bn_shape(a, who);
+static int check_bn_args(const dd3d_tower_bn_args* a, const char* who, int need, bool wide = false) {
+  const int rc = check_bn_shape(a, who, wide);
   if (rc != DD3D_OK) return rc;
   DD3D_REQUIRE(a->c_pitch % 4 == 0 && a->c_pitch >= a->C, "%s: c_pitch = %d must be a multiple of 4 and hold %d channels", who, a->c_pitch, a->C);
   if (need & 1) DD3D_REQUIRE(a->g_pitch % 4 == 0 && a->g_pitch >= a->C, "%s: g_pitch = %d must be a multiple of 4 and hold %d channels", who, a->g_pitch, a->C);

@@ -23,10 +23,67 @@ class BackboneLowering:
         """BasicBlock (dla.py:50-62): conv1+norm+relu, conv2+norm (+residual) relu.  `join`: side branch that produces the
         residual; it runs beside conv1."""
         mid = self.buf(name + ".mid", out.B, out.H, out.W, m.conv1.out_channels, kind="planes")  # conv1 -> conv2 only
+        if self._bbn:  # batch statistics: relu(n1), then relu(n2 + residual), each behind its raw convolution
+            self._bn_conv(m.conv1, x, mid.view(), hip.BBN_RELU, name + ".conv1")
+            self._bn_conv(m.conv2, mid.view(), out, hip.BBN_RESIDUAL, name + ".conv2", res=residual)
+            return
         self.conv_module(m.conv1, x, mid.view(), relu=True, name=name + ".conv1")
         if join is not None:
             self.join(join)
         self.conv_module(m.conv2, mid.view(), out, relu=True, res=residual, name=name + ".conv2", write_f32=out_f32)
+
+    @property
+    def _bbn(self):
+        """LossPlan(backbone_batch_stats=True): the bottom-up network's norms on the batch's statistics."""
+        return bool(getattr(self, "with_backbone_batch_stats", False))
+
+    def _bn_conv(self, conv, vin, out, act, name, res=None):
+        """One convolution of the bottom-up network with its BatchNorm2d on the batch's statistics (csrc/backbone_bn.hip): three ops --
+        `<name>.raw`, the convolution's raw f32 result (scale ones, no norm, no ReLU, no residual; `descaled` makes it the exact-f32
+        convolution) into a buffer of its own, `<name>.bn_stats` (dd3d_backbone_bn_batch_stats) and `<name>.bn_apply`
+        (dd3d_backbone_bn_apply: relu(n), n or relu(n + res)) into `out`, in whatever storages `out` has -- split planes and / or f32, a
+        channel slice of a root's concat buffer included: everything downstream reads what the running-statistics lowering would have
+        left there.  Every layer keeps its raw tensor (the norm's backward reads c where the ReLU clipped y).  Records what the backward
+        and the read-out need in `self.backbone_bn[name]`."""
+        from dd3d_amd.engine.losses import act_binding
+        from dd3d_amd.layers import BatchNorm2d
+        norm, Cc, dev = conv.norm, out.C, self.device
+        assert isinstance(norm, BatchNorm2d), f"backbone_batch_stats needs BatchNorm2d norms in the bottom-up network (FE.BACKBONE.NORM: BN): {name}"
+        assert hip.backbone_bn_width_ok(Cc) and Cc == conv.out_channels, (name, Cc)
+        raw = self.buf(name + ".raw", out.B, out.H, out.W, Cc).view()
+        shift = conv.bias.detach().float().cpu() if conv.bias is not None else torch.zeros(Cc)
+        self.conv_module(conv, vin, raw, relu=False, name=name + ".raw", fold=(torch.ones(Cc), shift))
+        N = out.B * out.H * out.W
+        stats = torch.zeros((hip.BN_STAT_ROWS, Cc), dtype=torch.float32, device=dev)
+        rows = hip.bn_slices([N])
+        assert self.backbone_bn_part.numel() >= rows * 2 * Cc, (name, rows, Cc)
+        f = hip.BackboneBnArgs()
+        a = f.bn
+        vecs = [self._vec(v) for v in (norm.weight, norm.bias, norm.running_mean, norm.running_var)]
+        a.c[0], a.stats[0], a.N[0] = raw.ptr, stats.data_ptr(), N
+        a.gamma[0], a.beta[0], a.run_mean[0], a.run_var[0] = (v.data_ptr() for v in vecs)
+        a.part, a.n_slices, a.status = self.backbone_bn_part.data_ptr(), self.backbone_bn_part.numel() // (2 * Cc), self.status.data_ptr()
+        a.num_segs, a.C, a.c_pitch = 1, Cc, raw.pitch
+        a.eps, a.momentum, a.plane_scale = float(norm.eps), hip.BN_MOMENTUM, float(out.buf.plane_scale)
+        if out.np and self.use_planes:  # split planes, and the f32 twin where the buffer has one
+            a.math_mode, a.y[0] = self.math, out.pptr or None
+            f.y32[0], f.y32_pitch = ((out.ptr or None) if out.has_f32 else None), out.pitch
+        else:
+            assert out.has_f32, name
+            a.math_mode, a.y[0], a.y_pitch = hip.MATH_F32, out.ptr or None, out.pitch
+        f.act, f.res_plane_scale = int(act), 1.0
+        if act == hip.BBN_RESIDUAL:
+            assert res is not None and (res.B, res.H, res.W, res.C) == (out.B, out.H, out.W, Cc), name
+            mode, addr, pitch, scale = act_binding(self, res)
+            f.res[0], f.res_mode, f.res_pitch, f.res_plane_scale = addr or None, int(mode), int(pitch), float(scale)
+        desc = dict(raw=raw, out=out, norm=norm, act=int(act), res=res, stats=stats)
+        op = CallOp(lambda lib, st_, f=f: hip.check(lib.dd3d_backbone_bn_batch_stats(C.byref(f.bn), st_), f"backbone_bn_batch_stats {name}"),
+                    f"{name}.bn_stats", dict(desc, kind="backbone_bn_batch_stats"))
+        op.keep = [stats] + vecs
+        self.ops.append(op)
+        self.ops.append(CallOp(lambda lib, st_, f=f: hip.check(lib.dd3d_backbone_bn_apply(C.byref(f), st_), f"backbone_bn_apply {name}"),
+                               f"{name}.bn_apply", dict(desc, kind="backbone_bn_apply")))
+        self.backbone_bn[name] = dict(conv=conv, norm=norm, raw=raw, out=out, stats=stats, act=int(act), args=f)
 
     @property
     def _twin(self):
@@ -64,8 +121,11 @@ class BackboneLowering:
                     bottom = x
             if m.project is not None:
                 residual = self.buf(name + ".proj", B, Ho, Wo, oc, kind="planes" if self.planes_only else "f32").view()
-                with self.branch(1):
-                    self.conv_module(m.project, bottom, residual, name=name + ".project")
+                if self._bbn:  # (no ReLU behind this norm: negative values are stored)
+                    self._bn_conv(m.project, bottom, residual, hip.BBN_LINEAR, name + ".project")
+                else:
+                    with self.branch(1):
+                        self.conv_module(m.project, bottom, residual, name=name + ".project")
                 side = 1
             else:
                 residual = bottom
@@ -74,7 +134,10 @@ class BackboneLowering:
             self._block(m.tree2, x1, x1, x2, name + ".tree2", out_f32=not x2.np)  # x2 only feeds the root (planes)
             if dst is None:
                 dst = self.buf(name + ".out", B, Ho, Wo, oc, kind=self._twin).view()  # next level: conv input + max-pool input
-            self.conv_module(m.root.conv, cat.view(), dst, relu=True, name=name + ".root")
+            if self._bbn:
+                self._bn_conv(m.root.conv, cat.view(), dst, hip.BBN_RELU, name + ".root")
+            else:
+                self.conv_module(m.root.conv, cat.view(), dst, relu=True, name=name + ".root")
             return dst
         assert m.levels == 2, "DLA-34 only nests trees two deep"
         cat2 = self.buf(name + ".cat", B, Ho, Wo, m.tree2.root_dim, kind=self._twin)
@@ -151,6 +214,8 @@ class BackboneLowering:
         import os
         if self.math != hip.MATH_F16X2 or os.environ.get("DD3D_FUSED_STEM", "1") == "0" or self.Hp % 2 or self.Wp % 2:
             return False
+        if self._bbn:  # base_layer and level0 never leave LDS there: no batch statistics to take
+            return False
         convs = [dla.base_layer] + list(dla.level0) + list(dla.level1)
         want = [(16, 3, 7, 1, 3), (16, 16, 3, 1, 1), (32, 16, 3, 2, 1)]
         if len(convs) != 3:
@@ -164,6 +229,14 @@ class BackboneLowering:
     def _dla(self, dla, img):
         B, H, W = self.B, self.Hp, self.Wp
         ch = dla.channels
+        if self._bbn:
+            assert not self.fused_stem
+            # One scratch of slice partials for every norm, forward and backward: they run in stream order on the main stream (side
+            # branches, an opt-in of the running-statistics lowering, are off in this plan).  The widest user is a full-resolution layer.
+            self.use_branches = False
+            need = max(hip.bn_slices([B * -(-H // 2**i) * -(-W // 2**i)]) * 2 * c for i, c in enumerate(ch))
+            self.backbone_bn_part = torch.zeros(need, dtype=torch.float32, device=self.device)
+            self.backbone_bn = OrderedDict()
         if self.fused_stem:
             y = self.buf("level1.0", B, H // 2, W // 2, ch[1], kind=self._twin)  # level2: conv input + max-pool input
             keep = None
@@ -174,16 +247,22 @@ class BackboneLowering:
             self.ops.append(stem)
             x = y.view()
         else:
+            def stem_conv(conv, vin, vout, name):
+                if self._bbn:
+                    self._bn_conv(conv, vin, vout, hip.BBN_RELU, name)
+                else:
+                    self.conv_module(conv, vin, vout, relu=True, name=name)
+
             base = self.buf("base", B, H, W, ch[0])
-            self.conv_module(dla.base_layer, img, base.view(), relu=True, name="base_layer")
+            stem_conv(dla.base_layer, img, base.view(), "base_layer")
             x = base.view()
             for i, conv in enumerate(dla.level0):
                 y = self.buf(f"level0.{i}", B, H, W, ch[0])
-                self.conv_module(conv, x, y.view(), relu=True, name=f"level0.{i}")
+                stem_conv(conv, x, y.view(), f"level0.{i}")
                 x = y.view()
             for i, conv in enumerate(dla.level1):
                 y = self.buf(f"level1.{i}", B, x.H // conv.stride, x.W // conv.stride, ch[1], kind="both")  # level2: conv input + max-pool input
-                self.conv_module(conv, x, y.view(), relu=True, name=f"level1.{i}")
+                stem_conv(conv, x, y.view(), f"level1.{i}")
                 x = y.view()
         outs = {"level0": None, "level1": x}
         from dd3d_amd.modeling.dla import BasicBlock

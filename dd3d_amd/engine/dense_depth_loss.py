@@ -92,14 +92,15 @@ class DenseDepthLossPlan(BackwardStages, DenseDepthPlan):
     refuses): `pred_grads` the one predictor group (n = 1 at pitch 4, a filter per level, Scale / Offset in slot 0), `tower_grads` the
     box3d tower, `fpn_grads` the FPN, `backbone_grads` / `stem_grads` DLA-34, `vovnet_grads` / `vovnet_stem_grads` the VoVNet-V2
     backbones; `batch_stats` normalises a trainable-BatchNorm2d tower with the batch's statistics, forward and backward, `fpn_batch_stats`
-    the FPN's lateral and output norms (FE.FPN.NORM: BN).  From
+    the FPN's lateral and output norms (FE.FPN.NORM: BN), `backbone_batch_stats` DLA-34's (FE.BACKBONE.NORM: BN).  From
     `tower_grads` on every tower layer keeps its output (5 levels x NUM_CONVS buffers of 256 channels in place of the two ping / pong
     sets); every other plan launches exactly what it launched before these flags existed."""
     def __init__(self, model, B, Hp, Wp, device=None, dry_run=False, head_grads=False, pred_grads=False, tower_grads=False, fpn_grads=False,
-                 backbone_grads=False, stem_grads=False, vovnet_grads=False, vovnet_stem_grads=False, batch_stats=False, fpn_batch_stats=False):
+                 backbone_grads=False, stem_grads=False, vovnet_grads=False, vovnet_stem_grads=False, batch_stats=False, fpn_batch_stats=False,
+                 backbone_batch_stats=False):
         self._chain_flags(model, B, Hp, Wp, grads=head_grads, pred_grads=pred_grads, tower_grads=tower_grads, fpn_grads=fpn_grads,
                           backbone_grads=backbone_grads, stem_grads=stem_grads, vovnet_grads=vovnet_grads, batch_stats=batch_stats,
-                          vovnet_stem_grads=vovnet_stem_grads, fpn_batch_stats=fpn_batch_stats)
+                          vovnet_stem_grads=vovnet_stem_grads, fpn_batch_stats=fpn_batch_stats, backbone_batch_stats=backbone_batch_stats)
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
         weight, beta, min_depth, max_depth = dense_depth_loss_config(model.cfg)  # (read here, not in the model's constructor)
         self.adopt_weight_store(model)

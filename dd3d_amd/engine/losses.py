@@ -7,7 +7,7 @@ and the stem's output (csrc/backbone_grads.hip), and last through the stem -- ba
 (csrc/stem_grads.hip); for the VoVNet-V2 backbones, behind the FPN through stage5 .. stage2, stem_3 and stem_2 (csrc/vovnet_grads.hip and
 the wide entry points of csrc/backbone_grads.hip) and last stem_1's filter (dd3d_vovnet_stem_wgrad, csrc/stem_grads.hip).  With
 batch_stats=True the head towers whose norm is a trainable BatchNorm2d use the batch's statistics, forward and backward
-(csrc/tower_bn.hip); with fpn_batch_stats=True the FPN's lateral and output norms do (csrc/fpn_bn.hip).  There is no optimiser or model.train().  The chain behind the loss backward (flags, stage builders, read-outs) is the
+(csrc/tower_bn.hip); with fpn_batch_stats=True the FPN's lateral and output norms do (csrc/fpn_bn.hip), with backbone_batch_stats=True the DLA-34 bottom-up network's (csrc/backbone_bn.hip).  There is no optimiser or model.train().  The chain behind the loss backward (flags, stage builders, read-outs) is the
 mixin ``BackwardStages``: ``LossPlan`` and the dense-depth network's ``DenseDepthLossPlan`` (dense_depth_loss.py) both run it.
 
 ``LossPlan`` reuses the forward plan's trunk and heads (ForwardPlan._trunk / _heads) and, in place of the inference post-processing,
@@ -727,6 +727,70 @@ class FpnBnGrads(TowerBnGrads):
                               guard=guard)
 
 
+class BackboneBnGrads(TowerBnGrads):
+    """The norm backward of ONE convolution of the DLA-34 bottom-up network under backbone_batch_stats (csrc/backbone_bn.hip; the widths
+    16 .. 512): one segment.  `y`: (mode, device address, pitch, plane scale) of the stored tensor whose sign masks `g` -- the layer's own
+    output behind a ReLU, the block's output for a project (its gradient is the residual's share G * [x1 > 0]) -- or None for no mask.
+    qp [1, 2, C] holds (d beta, d gamma), gc[0] the dense gradient [B, h, w, C] at the raw convolution output."""
+    ENTRIES = (("dd3d_backbone_bn_backward_reduce", "backbone_bn_backward_reduce"), ("dd3d_backbone_bn_backward_apply", "backbone_bn_backward_apply"))
+    LINEAR = (("dd3d_backbone_bn_backward_reduce_linear", "backbone_bn_backward_reduce_linear"),
+              ("dd3d_backbone_bn_backward_apply_linear", "backbone_bn_backward_apply_linear"))
+
+    def __init__(self, device, B, hw, Cc, raw, y, g, stats, part, fill=0.0, guard=0):
+        assert tuple(g.shape) == (B, hw[0], hw[1], Cc) and g.stride(-1) == 1, (tuple(g.shape), (B, hw[0], hw[1], Cc))
+        self.masked = y is not None
+        if not self.masked:
+            self.ENTRIES = self.LINEAR
+        TowerBnGrads.__init__(self, device, B, [hw], Cc, [raw], [y if self.masked else (hip.PG_ACT_F32, 0, 0, 1.0)], [g], self.pitch(g), [stats], part,
+                              fill=fill, guard=guard)
+
+
+def check_backbone_batch_stats(model, B, Hp, Wp, stem_grads=False):
+    """What LossPlan(backbone_batch_stats=True) refuses before anything is built: a bottom-up network without trainable BatchNorm2d (the
+    flag must not be a silent no-op), everything but the DLA-34 lowering (VoVNet, the Bottleneck variants, force_generic_dla), a level
+    with one value per channel (in torch's words), the arithmetic modes and lowerings without split planes, and an odd canvas under
+    stem_grads."""
+    import os
+    from dd3d_amd.modeling.dla import DLA, BasicBlock
+    cfg, net = model.cfg, model.backbone.bottom_up
+    if str(cfg.FE.BACKBONE.NORM) != "BN":
+        raise ValueError(f"backbone_batch_stats needs FE.BACKBONE.NORM = 'BN' (it is {str(cfg.FE.BACKBONE.NORM)!r}): the bottom-up network has no norm "
+                         "that uses batch statistics")
+    if not isinstance(net, DLA):
+        raise NotImplementedError(f"backbone_batch_stats covers the DLA-34 bottom-up network; {type(net).__name__} (the VoVNet-V2 family) has no "
+                                  "batch-statistics lowering")
+    if net.block is not BasicBlock:
+        raise NotImplementedError(f"backbone_batch_stats covers BasicBlock trees (DLA-34); the {net.block.__name__} DLA variants have no "
+                                  "batch-statistics lowering")
+    if max(net.levels) > 2 or net.residual_root:
+        raise NotImplementedError("backbone_batch_stats covers trees at most two deep without a residual root (DLA-34)")
+    if getattr(model, "force_generic_dla", False):
+        raise NotImplementedError("backbone_batch_stats follows the DLA-34 lowering; force_generic_dla has no batch-statistics form")
+    bad = [int(c) for c in net.channels if not hip.backbone_bn_width_ok(int(c))]
+    if bad:
+        raise NotImplementedError(f"backbone_batch_stats takes 16, multiples of 32 up to 256 and multiples of 256 up to {hip.BBN_MAX_C} channels "
+                                  f"(a level has {bad[0]})")
+    mode = plan_math(model)
+    if mode in (hip.MATH_BF16X2, hip.MATH_BF16):
+        name = {hip.MATH_BF16X2: "bf16x2", hip.MATH_BF16: "bf16"}[mode]
+        raise NotImplementedError(f"backbone_batch_stats stores f16x2 or bf16x3 planes; the arithmetic mode {name!r} has no apply")
+    for on, what in ((mode == hip.MATH_F32, "DD3D_MATH=f32"), (mode == hip.MATH_BF16X3 and os.environ.get("DD3D_PLANES", "1") == "0", "DD3D_PLANES=0"),
+                     (os.environ.get("DD3D_PLANES_ONLY", "1") == "0", "DD3D_PLANES_ONLY=0")):
+        if on:
+            raise NotImplementedError(f"backbone_batch_stats is built on the split-plane trees; {what} selects a lowering with f32 twins, which has "
+                                      "no batch-statistics form")
+    if stem_grads and (int(Hp) % 2 or int(Wp) % 2):
+        raise NotImplementedError(f"backbone_batch_stats with stem gradients needs an even canvas ({Hp} x {Wp}): the stem's lowering sizes level1 as "
+                                  "floor(H / 2), the stride-2 backward as ceil(H / 2)")
+    h, w = int(Hp), int(Wp)
+    for i, c in enumerate(net.channels):
+        if i:
+            h, w = h // 2, w // 2
+        if B * h * w < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size [{B}, {c}, {h}, {w}] "
+                             f"(level{i} of the bottom-up network on a {Hp} x {Wp} canvas)")
+
+
 def plan_math(model):
     """The DD3D_MATH_* a plan of `model` will run on (ForwardPlan._trunk's rule), known before the plan exists."""
     from dd3d_amd.engine.tiling import MATH_NAMES, default_math
@@ -734,7 +798,7 @@ def plan_math(model):
     return default_math() if m is None else MATH_NAMES[m] if isinstance(m, str) else int(m)
 
 
-def check_fpn_batch_stats(model, B, Hp, Wp):
+def check_fpn_batch_stats(model, B, Hp, Wp, backbone_covered=False):
     """What LossPlan(fpn_batch_stats=True) refuses before anything is built: an FPN without trainable BatchNorm2d (the flag must not be a
     silent no-op), a bottom-up network that would need batch statistics too, a stage with one value per channel (in torch's words),
     widths the kernels do not take, another fuse type, and the lowerings without the fused split-plane FPN."""
@@ -743,7 +807,7 @@ def check_fpn_batch_stats(model, B, Hp, Wp):
     cfg, fpn = model.cfg, model.backbone
     if str(cfg.FE.FPN.NORM) != "BN":
         raise ValueError(f"fpn_batch_stats needs FE.FPN.NORM = 'BN' (it is {str(cfg.FE.FPN.NORM)!r}): the FPN has no norm that uses batch statistics")
-    if str(cfg.FE.BACKBONE.NORM) == "BN":
+    if str(cfg.FE.BACKBONE.NORM) == "BN" and not backbone_covered:  # (backbone_batch_stats=True gives the bottom-up network's)
         raise NotImplementedError("fpn_batch_stats covers the FPN; FE.BACKBONE.NORM = 'BN' would need batch statistics in the bottom-up network as well")
     if fpn._fuse_type != "sum":
         raise NotImplementedError(f"fpn_batch_stats implements FE.FPN FUSE_TYPE 'sum' (it is {fpn._fuse_type!r})")
@@ -766,13 +830,14 @@ def check_fpn_batch_stats(model, B, Hp, Wp):
                                       "batch-statistics form (separate top-down launches on f32 laterals)")
 
 
-def check_batch_stats(model, B, Hp, Wp, fpn_covered=False):
+def check_batch_stats(model, B, Hp, Wp, fpn_covered=False, backbone_covered=False):
     """What LossPlan(batch_stats=True) refuses before anything is built: a level with one value per channel (the reference raises there
-    too, in torch's words) and trunk norms that would need batch statistics as well (`fpn_covered`: fpn_batch_stats=True gives the FPN's)."""
+    too, in torch's words) and trunk norms that would need batch statistics as well (`fpn_covered`: fpn_batch_stats=True gives the FPN's;
+    `backbone_covered`: backbone_batch_stats=True the bottom-up network's)."""
     import math
     cfg = model.cfg
     for key, node in (("FE.BACKBONE.NORM", cfg.FE.BACKBONE), ("FE.FPN.NORM", cfg.FE.FPN)):
-        if str(node.NORM) == "BN" and not (fpn_covered and key == "FE.FPN.NORM"):
+        if str(node.NORM) == "BN" and not (fpn_covered and key == "FE.FPN.NORM") and not (backbone_covered and key == "FE.BACKBONE.NORM"):
             raise NotImplementedError(f"batch_stats covers the head towers; {key} = 'BN' would need batch statistics in the trunk as well")
     for s in model.backbone_output_shape:
         h, w = math.ceil(Hp / s.stride), math.ceil(Wp / s.stride)
@@ -841,7 +906,7 @@ def dla_slab_words(B, dla, H1, W1):
     return rows, qrows
 
 
-def dla_backward(device, B, dla, G, acts, vec, slab=None, fill=0.0, guard=0):
+def dla_backward(device, B, dla, G, acts, vec, slab=None, fill=0.0, guard=0, bn=None):
     """The calls of the DLA-34 backward in their order, level5 down to level2 (include/dd3d_hip.h states the mathematics).  Per depth-1
     tree: root, tree2.conv2, tree2.conv1, tree1.conv2, project, tree1.conv1, pool; a depth-2 tree runs its tree2 first, then its tree1.
 
@@ -849,7 +914,13 @@ def dla_backward(device, B, dla, G, acts, vec, slab=None, fill=0.0, guard=0):
     buffer of BackboneLowering._tree (<tree>.cat, <tree>.tree1.mid, <tree>.tree2.mid, <tree>.bottom, <tree>.out) and "level1" for the
     tensor level2 reads: ((mode, address, pitch, plane scale) of the WHOLE buffer, H, W, C)}; `vec`: host vector -> device.  Returns
     ({key: BackboneConvGrads or PoolGrads}, the gradient [B, h1, w1, C1] at the level1 tensor); a convolution's layer carries its module
-    as `conv` and what it reads as `src` = {operand: (buffer name, first channel, channels)}."""
+    as `conv` and what it reads as `src` = {operand: (buffer name, first channel, channels)}.
+
+    `bn` (backbone_batch_stats): dict(layers={key: dict(raw=(address, pitch), stats=tensor)}, part=scratch, ones={C: [C] ones}).  Then a
+    BackboneBnGrads sits between each layer's incoming gradient and its convolution gradients (the layer's `bn`, run in front of it): it
+    masks G by the stored tensor the running-statistics call would mask it by -- the layer's own output; for a project the block's
+    output x1, whose ReLU the residual's share crossed -- and returns G_c; the convolution calls run on g := G_c without a mask, scale
+    ones.  `add` and `res` (the residual's share G * [x1 > 0], masked on the way by the stored x1) are what they were."""
     from dd3d_amd.layers import fold_norm
     check_dla_backward(dla)
     layers, common = OrderedDict(), dict(fill=fill, guard=guard)
@@ -863,8 +934,16 @@ def dla_backward(device, B, dla, G, acts, vec, slab=None, fill=0.0, guard=0):
         k, cin, cout = int(mod.weight.shape[-1]), int(mod.weight.shape[1]), int(mod.weight.shape[0])
         assert x[2] == cin and (y is None or y[2] == cout), (key, x, y)
         H, W = acts[x[0]][1], acts[x[0]][2]
-        lay = BackboneConvGrads(device, B, H, W, cin, cout, k, stride, bind(x), bind(y) if y is not None else None, g, filter_copy(mod, device),
-                                vec(fold_norm(mod, None)[0]), add=add, res=(res[0], bind(res[1])) if res is not None else None, slab=slab, **common)
+        norm_call, yb, scale = None, bind(y) if y is not None else None, None
+        if bn is not None:
+            rec = bn["layers"][key]
+            norm_call = BackboneBnGrads(device, B, ((H + stride - 1) // stride, (W + stride - 1) // stride), cout, rec["raw"], yb, g, rec["stats"], bn["part"],
+                                        **common)
+            g, yb, scale = norm_call.gc[0], None, bn["ones"][cout]
+        lay = BackboneConvGrads(device, B, H, W, cin, cout, k, stride, bind(x), yb, g, filter_copy(mod, device),
+                                vec(fold_norm(mod, None)[0]) if scale is None else scale, add=add, res=(res[0], bind(res[1])) if res is not None else None,
+                                slab=slab, **common)
+        lay.bn = norm_call
         lay.conv, lay.norm, lay.src = mod, getattr(mod, "norm", None), dict(x=x, y=y, res_y=res[1] if res is not None else None)
         layers[key] = lay
         return lay.da
@@ -949,8 +1028,18 @@ def dla_param_grads(named, layers, prefix=""):
     """{parameter name: gradient of the parameter's shape} from the layers of `dla_backward`; `named`: {id(parameter): name}."""
     params = {}
     for lay in layers.values():
-        if getattr(lay, "conv", None) is not None:
+        if getattr(lay, "conv", None) is None:
+            continue
+        norm_call = getattr(lay, "bn", None)
+        if norm_call is None:
             params.update(conv_param_grads(named, lay, lay.conv, lay.norm, lay.dw, lay.scale, lay.q, lay.r))
+            continue
+        # batch statistics: d gamma = p, d beta = q of the norm's backward; the convolution call's own q / r are by-products (q: the sum
+        # of G_c, a conv bias' gradient -- zero up to rounding, the norm removes the mean)
+        params.update(conv_param_grads(named, lay, lay.conv, None, lay.dw, lay.scale, lay.q, lay.r))
+        for p, v in ((lay.norm.weight, norm_call.qp[0, 1]), (lay.norm.bias, norm_call.qp[0, 0])):
+            if id(p) in named:
+                params[named[id(p)]] = v.clone()
     return params
 
 
@@ -1263,16 +1352,20 @@ class BackwardStages:
     A plan mixes this in beside its forward plan; what it must provide: `tower_info`, `tower_out`, `pred_info`, `tower_bn` / `bn_part` as
     ForwardPlan._heads records them, `_pred_group_table` (what the predictor groups bind), and `grads` handled by its own loss backward."""
     def _chain_flags(self, model, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
-                     stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False, fpn_batch_stats=False):
+                     stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False, fpn_batch_stats=False,
+                     backbone_batch_stats=False):
         """The flags of the chain, each implying the shallower ones, and what they refuse before anything is built or launched."""
         self.batch_stats = bool(batch_stats)
         self.with_fpn_batch_stats = bool(fpn_batch_stats)  # (`fpn_batch_stats` itself is the read-out method; read by the trunk: _fpn)
-        if self.batch_stats and not self.with_fpn_batch_stats:  # before anything is built or launched
-            check_batch_stats(model, B, Hp, Wp)
+        self.with_backbone_batch_stats = covered = bool(backbone_batch_stats)  # (likewise; read by the trunk: _dla)
+        if covered:  # before anything is built or launched
+            check_backbone_batch_stats(model, B, Hp, Wp, stem_grads=bool(stem_grads))
+        if self.batch_stats and not self.with_fpn_batch_stats:
+            check_batch_stats(model, B, Hp, Wp, backbone_covered=covered)
         if self.with_fpn_batch_stats:
-            check_fpn_batch_stats(model, B, Hp, Wp)
+            check_fpn_batch_stats(model, B, Hp, Wp, backbone_covered=covered)
             if self.batch_stats:  # (FE.FPN.NORM = BN is what the other flag covers)
-                check_batch_stats(model, B, Hp, Wp, fpn_covered=True)
+                check_batch_stats(model, B, Hp, Wp, fpn_covered=True, backbone_covered=covered)
         self.with_vovnet_stem_grads = bool(vovnet_stem_grads)  # (`vovnet_stem_grads` itself is the read-out method)
         self.with_vovnet_grads = bool(vovnet_grads) or self.with_vovnet_stem_grads  # (`vovnet_grads` itself is the read-out method)
         if self.with_vovnet_grads:  # before anything is built or launched
@@ -1560,9 +1653,23 @@ class BackwardStages:
         acts = {k: (act_binding(self, v), v.H, v.W, v.C) for k, v in views.items()}
         G = self._feature_grad_inputs()
         self._grow_slab(*dla_slab_words(B, dla, l1.H, l1.W))
-        self.backbone_layers, self.level1_grad = dla_backward(dev, B, dla, G, acts, self._vec, slab=self.tower_slab)
-        self._append_calls("backbone_grads", self.backbone_layers)
+        bn = None
+        if self.with_backbone_batch_stats:  # the norms' backward reads every layer's stored raw convolution output and statistics
+            self.backbone_bn_ones = {c: self._vec(torch.ones(c)) for c in sorted({int(c) for c in dla.channels})}
+            bn = dict(layers={k: dict(raw=(rec["raw"].ptr, rec["raw"].pitch), stats=rec["stats"]) for k, rec in self.backbone_bn.items()},
+                      part=self.backbone_bn_part, ones=self.backbone_bn_ones)
+            self.backbone_bn_reads = self._check_reads("backbone norm", [rec["raw"] for rec in self.backbone_bn.values()])
+        self.backbone_layers, self.level1_grad = dla_backward(dev, B, dla, G, acts, self._vec, slab=self.tower_slab, bn=bn)
+        self._append_norm_and_conv_calls("backbone", self.backbone_layers)
         self.backbone_reads = self._check_reads("backbone", views, self.backbone_layers)
+
+    def _append_norm_and_conv_calls(self, stage, layers):
+        """_append_calls, with each layer's norm backward (backbone_batch_stats: `lay.bn`) in front of the call that reads its G_c."""
+        for key, lay in layers.items():
+            norm_call = getattr(lay, "bn", None)
+            if norm_call is not None:
+                self.ops.append(CallOp(lambda lib, st, b=norm_call: b.launch(lib, st), f"{stage}_bn_grads.{key}", dict(kind=f"{stage}_bn_grads", layer=key)))
+            self._append_calls(f"{stage}_grads", {key: lay})
 
     def backbone_grads(self):
         """(the gradient at the stem's stored output, backbone parameter gradients) of the last run, copies: {backbone_level1: (B, C1,
@@ -1586,6 +1693,10 @@ class BackwardStages:
         part, qpart = self.tower_slab
         self.stem_layers = OrderedDict()
         g = self.level1_grad
+        bbn, ones_y = self.with_backbone_batch_stats, None
+        if bbn:  # the convolution calls run on G_c: as the stored output whose sign masks it, a plan-owned f32 tensor of ones (the towers' way)
+            self.stem_ones = torch.ones(max(self.bufs[y].t.numel() for _, _, _, y in convs), dtype=torch.float32, device=dev)
+            ones_y = lambda c: (hip.PG_ACT_F32, self.stem_ones.data_ptr(), int(c), 1.0)
         for key, conv, xname, yname in reversed(convs):
             xb, yv = self.bufs[xname], self.bufs[yname].view()
             cout, cin, k = int(conv.weight.shape[0]), int(xb.pitch), int(conv.weight.shape[-1])
@@ -1594,12 +1705,18 @@ class BackwardStages:
             n = hip.stem_grad_slices(B, xb.H, xb.W, cin, cout, k, int(conv.stride))
             assert n * cout * k * k * cin <= part.numel() and n * cout <= qpart.numel(), \
                 f"stem_grads.{key}: {n} slices of {cout} x {k * k * cin} words do not fit the plan's slab of {part.numel()} words"
-            lay = StemConvGrads(dev, B, xb.H, xb.W, cin, cout, k, int(conv.stride), xb.t, act_binding(self, yv), g, w, self._vec(fold_norm(conv, None)[0]),
-                                slab=self.tower_slab, dgrad=key != "base_layer")
+            norm_call, yb, scale = None, act_binding(self, yv), None
+            if bbn:
+                rec = self.backbone_bn[key]
+                norm_call = BackboneBnGrads(dev, B, (yv.H, yv.W), cout, (rec["raw"].ptr, rec["raw"].pitch), yb, g, rec["stats"], self.backbone_bn_part)
+                g, yb, scale = norm_call.gc[0], ones_y(cout), self.backbone_bn_ones[cout]
+            lay = StemConvGrads(dev, B, xb.H, xb.W, cin, cout, k, int(conv.stride), xb.t, yb, g, w,
+                                self._vec(fold_norm(conv, None)[0]) if scale is None else scale, slab=self.tower_slab, dgrad=key != "base_layer")
+            lay.bn = norm_call
             lay.conv, lay.norm, lay.src = conv, getattr(conv, "norm", None), dict(x=(xname, 0, cin), y=(yname, 0, cout))
             self.stem_layers[key] = lay
             g = lay.da
-        self._append_calls("stem_grads", self.stem_layers)
+        self._append_norm_and_conv_calls("stem", self.stem_layers)
         self.stem_reads = self._check_reads("stem", [self.bufs[n].view() for n in ("img4", "base", "level0.0", "level1.0")])
 
     def stem_grads(self):
@@ -1724,15 +1841,33 @@ class BackwardStages:
         return out
 
 
+    def backbone_batch_stats(self):
+        """The bottom-up network's batch statistics of the last run, copies keyed by the state-dict names of its norms
+        (`backbone.bottom_up.base_layer.norm`, `.level0.0.norm`, `.level1.0.norm`, `.level<n>...tree<k>.conv<j>.norm`, `...project.norm`,
+        `...root.conv.norm`): `.running_mean` / `.running_var` as one training step would leave them, `.batch_mean` / `.batch_var` the
+        batch's mean and biased variance (tower_batch_stats' conventions).  The model's own buffers are never written."""
+        if not self.with_backbone_batch_stats:
+            raise self._built_without("backbone_batch_stats")
+        names = {id(b): k for k, b in self.model.named_buffers()}
+        out = {}
+        for rec in self.backbone_bn.values():
+            norm, st = rec["norm"], rec["stats"]
+            mean_name, var_name = names[id(norm.running_mean)], names[id(norm.running_var)]
+            out[mean_name], out[var_name] = st[hip.BN_ROW_RUN_MEAN].clone(), st[hip.BN_ROW_RUN_VAR].clone()
+            stem = mean_name[:-len("running_mean")]
+            out[stem + "batch_mean"], out[stem + "batch_var"] = st[hip.BN_ROW_MU].clone(), st[hip.BN_ROW_VAR].clone()
+        return out
+
+
 class LossPlan(BackwardStages, ForwardPlan):
     """Trunk and heads of the forward plan, then GT assignment, the per-target loss terms and one finalize launch; captured as one
     hipGraph by DD3D.get_loss_plan.  `det_count` (what the read-back record carries beside the status word) holds the positive count."""
     def __init__(self, model, B, Hp, Wp, device=None, max_gt=hip.LOSS_MAX_GT, dry_run=False, grads=False, pred_grads=False, tower_grads=False,
                  fpn_grads=False, backbone_grads=False, stem_grads=False, vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False,
-                 fpn_batch_stats=False):
+                 fpn_batch_stats=False, backbone_batch_stats=False):
         self._chain_flags(model, B, Hp, Wp, grads=grads, pred_grads=pred_grads, tower_grads=tower_grads, fpn_grads=fpn_grads,
                           backbone_grads=backbone_grads, stem_grads=stem_grads, vovnet_grads=vovnet_grads, batch_stats=batch_stats,
-                          vovnet_stem_grads=vovnet_stem_grads, fpn_batch_stats=fpn_batch_stats)
+                          vovnet_stem_grads=vovnet_stem_grads, fpn_batch_stats=fpn_batch_stats, backbone_batch_stats=backbone_batch_stats)
         PlanBase.__init__(self, device or model.device, dry_run=dry_run)
         check_loss_config(model.cfg)
         from dd3d_amd.engine.tiling import default_tile_policy

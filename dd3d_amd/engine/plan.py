@@ -368,11 +368,12 @@ class PlanBase:
         return t.detach().float().contiguous().to(self.device)
 
     def conv_module(self, conv, vin, vout, relu=False, res=None, norm=None, name="", in_relu=False, weight=None, write_f32=True, write_planes=True,
-                    res_up=False):
-        """One Conv2d(+folded norm)(+residual)(+relu) as a single-segment launch.  `weight`: an OIHW filter to use instead of the
+                    res_up=False, fold=None):
+        """One Conv2d(+folded norm)(+residual)(+relu) as a single-segment launch.  `fold`: the epilogue's (scale, shift) in place of the
+        folded norm's (a raw convolution in front of a batch-statistics norm: ones and the conv bias).  `weight`: an OIHW filter to use instead of the
         module's (the same filter re-laid for a padded input layout, see `scatter_in_channels`).  `write_f32` / `write_planes`: drop
         one of the output buffer's storages for this producer (e.g. an f32 copy nobody reads)."""
-        scale, shift = fold_norm(conv, norm)
+        scale, shift = fold_norm(conv, norm) if fold is None else fold
         explicit = weight is not None
         weight = dense_filter(conv) if weight is None else weight
         N, Cin, KH, KW = weight.shape

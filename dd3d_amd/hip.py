@@ -433,6 +433,23 @@ class FpnBnArgs(C.Structure):
     ]
 
 
+BBN_MIN_C, BBN_MAX_C = 16, 512  # the widths of csrc/backbone_bn.hip: 16, multiples of 32 up to 256, multiples of 256 up to 512
+BBN_RELU, BBN_LINEAR, BBN_RESIDUAL = range(3)
+
+
+class BackboneBnArgs(C.Structure):
+    """`dd3d_backbone_bn_args`."""
+    _fields_ = [
+        ("bn", TowerBnArgs), ("y32", C.c_void_p * BN_MAX_SEGS), ("res", C.c_void_p * BN_MAX_SEGS), ("act", C.c_int32), ("res_mode", C.c_int32),
+        ("res_pitch", C.c_int32), ("y32_pitch", C.c_int32), ("res_plane_scale", C.c_float), ("reserved", C.c_int32)
+    ]
+
+
+def backbone_bn_width_ok(Cc):
+    """The rule of dd3d_backbone_bn_*: C = 16, a multiple of 32 up to 256, or a multiple of 256 up to 512."""
+    return Cc == BBN_MIN_C or (Cc >= 32 and Cc % 32 == 0 and Cc <= 256) or (Cc > 0 and Cc % 256 == 0 and Cc <= BBN_MAX_C)
+
+
 def bn_slices(pixels):
     """Rows of `part` one dd3d_bn_batch_stats / dd3d_bn_backward_reduce call needs for segments of `pixels` pixels each (the rule of
     dd3d_bn_slices, for plans built without a device)."""
@@ -456,7 +473,9 @@ EXPORTS = [
     "dd3d_vovnet_conv_wgrad", "dd3d_vovnet_conv_dgrad", "dd3d_vovnet_conv_grad_slices", "dd3d_vovnet_add", "dd3d_ese_backward", "dd3d_maxpool3x3s2_ceil_backward",
     "dd3d_vovnet_grad_layout",
     "dd3d_bn_batch_stats", "dd3d_bn_apply_relu_split", "dd3d_bn_backward_reduce", "dd3d_bn_backward_apply", "dd3d_bn_slices", "dd3d_tower_bn_layout",
-    "dd3d_bn_apply_topdown_split", "dd3d_bn_backward_reduce_linear", "dd3d_bn_backward_apply_linear", "dd3d_fpn_bn_layout"
+    "dd3d_bn_apply_topdown_split", "dd3d_bn_backward_reduce_linear", "dd3d_bn_backward_apply_linear", "dd3d_fpn_bn_layout",
+    "dd3d_backbone_bn_batch_stats", "dd3d_backbone_bn_apply", "dd3d_backbone_bn_backward_reduce", "dd3d_backbone_bn_backward_apply",
+    "dd3d_backbone_bn_backward_reduce_linear", "dd3d_backbone_bn_backward_apply_linear", "dd3d_backbone_bn_slices", "dd3d_backbone_bn_layout"
 ]
 
 
@@ -582,6 +601,13 @@ def lib():
     for name in ("dd3d_bn_backward_reduce_linear", "dd3d_bn_backward_apply_linear"):
         getattr(L, name).argtypes = [C.POINTER(TowerBnArgs), C.c_void_p]
     L.dd3d_fpn_bn_layout.argtypes = [C.c_void_p, C.c_int32]
+    for name in ("dd3d_backbone_bn_batch_stats", "dd3d_backbone_bn_backward_reduce", "dd3d_backbone_bn_backward_apply",
+                 "dd3d_backbone_bn_backward_reduce_linear", "dd3d_backbone_bn_backward_apply_linear"):
+        getattr(L, name).argtypes = [C.POINTER(TowerBnArgs), C.c_void_p]
+    L.dd3d_backbone_bn_apply.argtypes = [C.POINTER(BackboneBnArgs), C.c_void_p]
+    L.dd3d_backbone_bn_slices.argtypes = [C.POINTER(TowerBnArgs)]
+    L.dd3d_backbone_bn_slices.restype = C.c_int64
+    L.dd3d_backbone_bn_layout.argtypes = [C.c_void_p, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the .so is stale
     assert L.dd3d_abi_version() == ABI_VERSION, "libdd3d_hip.so ABI version mismatch; rebuild"

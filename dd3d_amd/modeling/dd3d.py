@@ -126,7 +126,7 @@ class DD3D(nn.Module):
         return plan
 
     def get_loss_plan(self, B, Hp, Wp, grads=False, pred_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False, stem_grads=False,
-                      vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False, fpn_batch_stats=False):
+                      vovnet_grads=False, batch_stats=False, vovnet_stem_grads=False, fpn_batch_stats=False, backbone_batch_stats=False):
         """The loss plan (engine.LossPlan) for one geometry, captured as one hipGraph; kept in the same bounded cache as the forward plans.
         `grads`: the plan that also runs the loss backward (head-map gradients); `pred_grads`: the plan that runs the predictor layer's
         backward behind it as well (parameter and tower-output gradients; implies `grads`); `tower_grads`: the plan that goes on through
@@ -141,7 +141,9 @@ class DD3D(nn.Module):
         `batch_stats`: the head towers whose norm is
         a trainable BatchNorm2d use the batch's statistics, as the reference's train() does (composes with every level above; a plan of
         its own beside the running-statistics one); `fpn_batch_stats`: the FPN's lateral and output norms (FE.FPN.NORM: BN) use the batch's
-        statistics (composes with every level above and with `batch_stats`; one more plan and cache key of its own)."""
+        statistics (composes with every level above and with `batch_stats`; one more plan and cache key of its own); `backbone_batch_stats`: the
+        norms of a DLA-34 bottom-up network (FE.BACKBONE.NORM: BN) use the batch's statistics (composes with every level above and with
+        both other norm flags; one more plan and cache key of its own)."""
         from dd3d_amd.engine.losses import LossPlan
         level = _deepest(vovnet_stem_grads=vovnet_stem_grads, vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads,
                          fpn_grads=fpn_grads, tower_grads=tower_grads, pred_grads=pred_grads, grads=grads)
@@ -150,6 +152,8 @@ class DD3D(nn.Module):
             key, level = key + ("batch_stats", ), dict(level, batch_stats=True)
         if fpn_batch_stats:
             key, level = key + ("fpn_batch_stats", ), dict(level, fpn_batch_stats=True)
+        if backbone_batch_stats:
+            key, level = key + ("backbone_batch_stats", ), dict(level, backbone_batch_stats=True)
         plan = self._plans.pop(key, None)
         if plan is None:
             plan = LossPlan(self, B, Hp, Wp, **level)
@@ -315,7 +319,7 @@ class DD3D(nn.Module):
     # ------------------------------------------------------------------ training losses (gradients: head maps and the predictor layer)
     @torch.no_grad()
     def compute_losses(self, batched_inputs, head_grads=False, predictor_grads=False, tower_grads=False, fpn_grads=False, backbone_grads=False,
-                       stem_grads=False, batch_stats=False, fpn_batch_stats=False, **branch):
+                       stem_grads=False, batch_stats=False, fpn_batch_stats=False, backbone_batch_stats=False, **branch):
         """The loss dict of the reference's training branch (core.py:95-112; NuscenesDD3D: nuscenes_dd3d.py:376-397) for a labelled batch:
         each item carries `image`, `intrinsics` and `instances` (gt_boxes, gt_classes, gt_boxes3d; nuScenes also gt_attributes,
         gt_speeds).  Values are 0-d float32 tensors on the model's device, keys in the reference's order.  Differences from the
@@ -377,12 +381,26 @@ class DD3D(nn.Module):
         flag is never a silent no-op), a stage with one value per channel ValueError in torch's words; FE.FPN.OUT_CHANNELS not a
         multiple of 32 or above 256, FUSE_TYPE avg, DD3D_PLANES=0, DD3D_PLANES_ONLY=0, DD3D_MATH=f32 and the reduced arithmetic modes
         raise NotImplementedError.  `batch_stats=True` alone keeps refusing FE.FPN.NORM = BN.
+        With `backbone_batch_stats` (it composes with every flag above, `batch_stats` and `fpn_batch_stats` included) every BatchNorm2d of a
+        DLA-34 bottom-up network under FE.BACKBONE.NORM: BN -- base_layer, level0, level1 and each tree's conv1 / conv2, project and
+        root.conv -- normalises its own convolution's raw output with the mean and biased variance over the B * h * w pixels of the
+        padded canvas (relu(n), n for a project, relu(n + residual) for a block's conv2), and the backward goes through both statistics
+        (csrc/backbone_bn.hip); the stem runs launch by launch (the fused stem keeps base_layer and level0 in LDS).  Keys and shapes of
+        every result stay; the bottom-up norms' .weight / .bias in `param_grads` are the norm backward's sums.
+        `plan.backbone_batch_stats()` returns the running statistics the step would leave and the batch's own; the model's buffers are
+        never written.  With all three norm flags a DLA-34 model with BN everywhere returns the loss dict and every parameter gradient
+        of the reference's train() step.  FE.BACKBONE.NORM other than BN raises ValueError naming the key; a VoVNet, the Bottleneck DLA
+        variants, force_generic_dla, DD3D_MATH=f32, DD3D_PLANES=0, DD3D_PLANES_ONLY=0 and the reduced arithmetic modes raise
+        NotImplementedError; a level with one value per channel raises ValueError in torch's words.  Without it `batch_stats` and
+        `fpn_batch_stats` keep refusing FE.BACKBONE.NORM = BN.
         The filter copies the backward reads are snapshots taken when the plan is built; there is no optimiser and no model.train().  V2-99, the Bottleneck DLA variants, force_generic_dla and the reduced arithmetic modes raise
         NotImplementedError."""
         from dd3d_amd.engine import relax_arithmetic
         vovnet_stem_grads = bool(branch.pop("vovnet_stem_grads", False))
         vovnet_grads = bool(branch.pop("vovnet_grads", False)) or vovnet_stem_grads
         norms = dict(batch_stats=batch_stats, fpn_batch_stats=True) if fpn_batch_stats else dict(batch_stats=batch_stats)
+        if backbone_batch_stats:
+            norms["backbone_batch_stats"] = True
         if branch:
             raise TypeError(f"compute_losses() got an unexpected keyword argument {next(iter(branch))!r}")
         gt = [x["instances"] for x in batched_inputs]

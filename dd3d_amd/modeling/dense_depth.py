@@ -162,15 +162,16 @@ class DD3DDenseDepth(nn.Module):
         deeper flags are DD3D.get_loss_plan's, each implying the shallower ones: one plan, and one cache key, per deepest requested level
         of the backward, and a further key under `batch_stats=True` (the box3d tower's trainable BatchNorm2d on the batch's statistics;
         the keyword is taken from `**norms`, any other extra keyword is a TypeError), and one more under `fpn_batch_stats=True` (the FPN's
-        norms under FE.FPN.NORM: BN; taken from `**norms` too)."""
+        norms under FE.FPN.NORM: BN; taken from `**norms` too) and under `backbone_batch_stats=True` (DLA-34's norms under FE.BACKBONE.NORM: BN)."""
         from dd3d_amd.engine import DenseDepthLossPlan
         batch_stats = bool(norms.pop("batch_stats", False))
         fpn_batch_stats = bool(norms.pop("fpn_batch_stats", False))
+        backbone_batch_stats = bool(norms.pop("backbone_batch_stats", False))
         if norms:
             raise TypeError(f"get_loss_plan() got an unexpected keyword argument {next(iter(norms))!r}")
         level = _deepest(vovnet_stem_grads=vovnet_stem_grads, vovnet_grads=vovnet_grads, stem_grads=stem_grads, backbone_grads=backbone_grads,
                          fpn_grads=fpn_grads, tower_grads=tower_grads, pred_grads=pred_grads, head_grads=head_grads)
-        if not batch_stats and not fpn_batch_stats and not set(level) - {"head_grads"}:  # the two keys from before the deeper levels existed
+        if not batch_stats and not fpn_batch_stats and not backbone_batch_stats and not set(level) - {"head_grads"}:  # the two keys from before the deeper levels existed
             return self._cached_plan(("dense_depth_loss_grads" if level else "dense_depth_loss", B, Hp, Wp, self.math),
                                      lambda: DenseDepthLossPlan(self, B, Hp, Wp, **level))
         key = ("dense_depth_loss", B, Hp, Wp, self.math) + tuple(level)
@@ -178,6 +179,8 @@ class DD3DDenseDepth(nn.Module):
             key, level = key + ("batch_stats", ), dict(level, batch_stats=True)
         if fpn_batch_stats:
             key, level = key + ("fpn_batch_stats", ), dict(level, fpn_batch_stats=True)
+        if backbone_batch_stats:
+            key, level = key + ("backbone_batch_stats", ), dict(level, backbone_batch_stats=True)
         return self._cached_plan(key, lambda: DenseDepthLossPlan(self, B, Hp, Wp, **level))
 
     @torch.no_grad()
@@ -203,7 +206,8 @@ class DD3DDenseDepth(nn.Module):
         (DD3D.FCOS3D.NORM: BN) normalises with the batch's statistics per layer, level and channel, and the backward differentiates
         through them; `get_loss_plan(..., batch_stats=True).tower_batch_stats()` returns them; the model's buffers are never written.
         `fpn_batch_stats` (taken from `**branch` as well; composes with every flag) does the same for the FPN's lateral and output norms
-        under FE.FPN.NORM: BN, with the refusals and the `fpn_batch_stats()` read-out of DD3D.compute_losses.
+        under FE.FPN.NORM: BN, with the refusals and the `fpn_batch_stats()` read-out of DD3D.compute_losses; `backbone_batch_stats`
+        (from `**branch` too) for the DLA-34 bottom-up network's norms under FE.BACKBONE.NORM: BN, read out by `backbone_batch_stats()`.
         What DD3D.compute_losses refuses is refused here in the same words (NotImplementedError: the Bottleneck DLA variants,
         force_generic_dla, the slim / depthwise VoVNet specs, the reduced arithmetic modes, backbone_grads on a VoVNet, vovnet_grads on a
         DLA, FE.BACKBONE.NORM / FE.FPN.NORM = BN under batch_stats).  The filter copies the backward reads are snapshots taken when the
@@ -211,6 +215,8 @@ class DD3DDenseDepth(nn.Module):
         from dd3d_amd.engine import relax_arithmetic
         batch_stats = bool(branch.pop("batch_stats", False))
         norms = dict(batch_stats=batch_stats, fpn_batch_stats=True) if branch.pop("fpn_batch_stats", False) else dict(batch_stats=batch_stats)
+        if branch.pop("backbone_batch_stats", False):
+            norms["backbone_batch_stats"] = True
         vovnet_stem_grads = bool(branch.pop("vovnet_stem_grads", False))
         vovnet_grads = bool(branch.pop("vovnet_grads", False)) or vovnet_stem_grads
         if branch:

@@ -1378,6 +1378,68 @@ int dd3d_bn_backward_reduce_linear(const dd3d_tower_bn_args* args, void* stream)
 int dd3d_bn_backward_apply_linear(const dd3d_tower_bn_args* args, void* stream);
 int dd3d_fpn_bn_layout(int64_t* out, int32_t n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batch-statistics BatchNorm of the DLA-34 bottom-up network (csrc/backbone_bn.hip): nn.BatchNorm2d in train() behind every convolution
+ * of base_layer, level0, level1 and the trees (dla.py:24-62, 146-167, 271-280).  A SEGMENT is one norm: N = B * h * w pixels of the
+ * padded canvas, C channels.  The mathematics is the towers' (above): mu, v in two passes, rstd, s, t, the running-statistics read-outs,
+ * n = fmaf(c - mu, s, beta).  What differs is the width -- C = DD3D_BBN_MIN_C (16: the stem), a multiple of 32 up to 256, or a multiple
+ * of 256 up to DD3D_BBN_MAX_C (512: level5) -- and what follows the norm:
+ *   act DD3D_BBN_RELU      y = relu(n)                       conv1 of a block, root.conv, the stem layers
+ *   act DD3D_BBN_LINEAR    y = n                             project (negative values are stored)
+ *   act DD3D_BBN_RESIDUAL  y = relu(n + r)                   conv2 of a BasicBlock; r the stored residual at the same pixel and channel,
+ *                                                            decoded from its storage res_mode (DD3D_PG_ACT_*: f32 NHWC of pitch res_pitch,
+ *                                                            or split planes of the slice's first chunk: (hi + lo) / res_plane_scale,
+ *                                                            (hi + mid) + lo -- what the convolution epilogue's res_mode 1 / 2 add), added
+ *                                                            in f32 before the ReLU
+ * Backward, with G the gradient at y: ghat = G * [stored y > 0] for RELU and RESIDUAL (y > 0 exactly where n + r > 0), ghat = G for
+ *   LINEAR; q = sum(ghat) = d beta, p = sum(ghat * xhat) = d gamma, G_c = s * (ghat - q / N - xhat * p / N).  The residual's own share,
+ *   G * [y > 0], is formed by the consumer of G (dd3d_backbone_dgrad's res_g / res_y), not here.
+ * Order of every sum: the towers' -- slices of DD3D_BN_SLICE consecutive pixels; inside a slice a channel has P = 256 / (min(C, 256) / 4)
+ *   thread lanes, lane j adds pixels j, j + P, ... in that order, the lanes are added in lane order; the slice partials are added by
+ *   eight lanes, lane j slices j, j + 8, ..., the lanes in lane order.  The sum ORDER IS KEPT: at C a multiple of 32 up to 256 the
+ *   statistics and the backward's q, p, G_c are the bits of dd3d_bn_batch_stats / dd3d_bn_backward_reduce / _apply (they run the same
+ *   kernels); C = 16 has P = 64 (one pixel per lane), C = 512 runs as two chunks of 256 channels with P = 4 each.  One writer per word,
+ *   no float atomics, the same bits on every run, safe under stream capture.
+ * dd3d_backbone_bn_batch_stats (four launches): bn-> every word of stats; reads c, gamma, beta, run_mean, run_var.
+ * dd3d_backbone_bn_apply (one launch, thread = (pixel, 8 channels), 16-byte loads and stores; at C = 16 two threads share a pixel, no
+ *   lane idles): y from bn.c, bn.beta, bn.stats rows MU, S and the residual.  Stores: bn.math_mode a split-plane mode -- bn.y[s]
+ *   (optional) the split planes [C/32][N][NP][32] of the slice's first chunk, bit for bit what dd3d_split_planes makes of the f32 value,
+ *   its DD3D_STATUS_F16_OVERFLOW bit in bn.status included; y32[s] (optional) f32 NHWC of pitch y32_pitch; at least one of the two; planes
+ *   need C % 32 == 0.  bn.math_mode DD3D_MATH_F32: bn.y[s] is f32 NHWC of pitch bn.y_pitch and y32 is not read.  An output may be a channel
+ *   slice of a wider buffer in either storage (f32: the pitch; planes: a run of whole chunk images of N pixels).
+ * dd3d_backbone_bn_backward_reduce / _apply: the masked backward (stored y in storage bn.y_mode, a channel slice allowed);
+ * dd3d_backbone_bn_backward_reduce_linear / _apply_linear: without the mask, the bits of the masked calls for a y of ones.
+ *   gc: f32 [N][C].  part: [n_slices][2][C], n_slices >= dd3d_backbone_bn_slices(args) = sum of ceil(N / DD3D_BN_SLICE).
+ * dd3d_backbone_bn_layout: sizeof and field offsets (layout check of the bindings; host only).
+ * Rejected (-1, dd3d_last_error starts with the entry point's name): what the tower entry points reject, with the widths above in place
+ *   of theirs; for the apply an unknown act, a RESIDUAL segment without res, an unknown res_mode, a res_pitch that is not a multiple of 4
+ *   or below C (f32 residual), a residual in planes at C % 32 != 0, a split-plane math_mode other than f16x2 / bf16x3, planes asked
+ *   for at C % 32 != 0, a segment with neither output, a y32 pitch that is not a multiple of 4 or below C.
+ * ------------------------------------------------------------------------------------------------ */
+#define DD3D_BBN_MIN_C 16
+#define DD3D_BBN_MAX_C 512
+#define DD3D_BBN_RELU 0
+#define DD3D_BBN_LINEAR 1
+#define DD3D_BBN_RESIDUAL 2
+typedef struct dd3d_backbone_bn_args { /* host memory; every pointer is device memory */
+  dd3d_tower_bn_args bn;               /* c, beta, stats, y, status, N, num_segs, C, c_pitch, math_mode, y_pitch, plane_scale */
+  float* y32[DD3D_BN_MAX_SEGS];        /* optional f32 copy of y beside the planes: [N][y32_pitch] */
+  const void* res[DD3D_BN_MAX_SEGS];   /* DD3D_BBN_RESIDUAL: the stored residual, first channel / first chunk of its slice */
+  int32_t act;                         /* DD3D_BBN_* */
+  int32_t res_mode, res_pitch;         /* DD3D_PG_ACT_*; floats per pixel of an f32 residual */
+  int32_t y32_pitch;
+  float res_plane_scale;               /* DD3D_PG_ACT_F16X2 */
+  int32_t reserved;                    /* 0; ignored */
+} dd3d_backbone_bn_args;
+int dd3d_backbone_bn_batch_stats(const dd3d_tower_bn_args* args, void* stream);
+int dd3d_backbone_bn_apply(const dd3d_backbone_bn_args* args, void* stream);
+int dd3d_backbone_bn_backward_reduce(const dd3d_tower_bn_args* args, void* stream);
+int dd3d_backbone_bn_backward_apply(const dd3d_tower_bn_args* args, void* stream);
+int dd3d_backbone_bn_backward_reduce_linear(const dd3d_tower_bn_args* args, void* stream);
+int dd3d_backbone_bn_backward_apply_linear(const dd3d_tower_bn_args* args, void* stream);
+int64_t dd3d_backbone_bn_slices(const dd3d_tower_bn_args* args);
+int dd3d_backbone_bn_layout(int64_t* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
